@@ -12,6 +12,10 @@ matrix (RCCL).  N is the job size at every GPU count => "scaling": "strong".
     python bench.py [--gpus N --steps K --warmup W] [--rows 1000000 --dim 1024 --centres 10000 --classes 30]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
+--steps K is the number of timed steps and `ms_per_step` the time of one of them.  --dump-outputs DIR writes what the
+last timed step computed (every class's alpha, the scores on a fixed row sample: dump_outputs) as .npy files, so that two
+builds run with the same arguments, and hence on the same inputs, can be compared output for output.
+
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself: the parent touches no
 GPU, runs `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process, relays rank 0's JSON line
 and exits with the child's status (no retry).
@@ -38,6 +42,7 @@ import torch.distributed as dist  # noqa: E402
 F32_MFMA_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: Peak FP32 (matrix)
 F16_MFMA_PEAK_TFLOPS = 2500.0  # same guide: Peak BF16/FP16 MFMA, dense
 HBM_PEAK_GBS = 8000.0          # HBM3E spec
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together
 
 
 def parse():
@@ -95,7 +100,16 @@ def parse():
     ap.add_argument("--emulate-rank", type=int, default=0, help="which rank of --emulate-world to run")
     ap.add_argument("--single-device", action="store_true",
                     help="debugging: every rank uses cuda:0 (exercises the sharded path on a 1-GPU box)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy: alpha (classes, M) "
+                    "f64, scores (rows, classes) f32 on a fixed seeded row sample when the whole matrix would not fit %d MB, "
+                    "score_rows (rows,) f64 = their global row indices" % (DUMP_BUDGET_BYTES // 10 ** 6))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be at least 0")
+    return args
 
 
 def synth_rows(n_lo, n_hi, D, C, seed, device):
@@ -251,6 +265,10 @@ def main():
         from odx.dist import EmulatedShard
         shard = EmulatedShard(args.emulate_world, args.emulate_rank)
     N, D, M, C = args.n, args.D, args.M, args.classes
+    if args.dump_outputs and 8 * C * M > DUMP_BUDGET_BYTES // 2:
+        print("bench.py: --dump-outputs: the alphas alone (%d x %d f64) exceed half of its %d-byte budget" % (C, M, DUMP_BUDGET_BYTES),
+              file=sys.stderr)
+        sys.exit(2)
     lo, hi = shard.bounds(N)
     n_loc = hi - lo
     seed = 1234 + 3
@@ -297,12 +315,12 @@ def main():
 
     main_stream = torch.cuda.Stream(priority=-1) if args.main_priority else None
 
-    def run_classes(classes, timed):
+    def run_classes(classes, timed, alphas_out=None):
         if main_stream is None:
-            return job.run(F, classes, phases=ph if timed else None, infos=infos if timed else None)
+            return job.run(F, classes, phases=ph if timed else None, infos=infos if timed else None, alphas_out=alphas_out)
         main_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(main_stream):
-            r = job.run(F, classes, phases=ph if timed else None, infos=infos if timed else None)
+            r = job.run(F, classes, phases=ph if timed else None, infos=infos if timed else None, alphas_out=alphas_out)
         torch.cuda.current_stream().wait_stream(main_stream)
         return r
 
@@ -336,10 +354,11 @@ def main():
 
     # ---- timed region: exactly K steps
     t0 = time.perf_counter()
-    last = None
+    last = alphas = None
     for _ in range(args.steps):
         F = be.features(X)       # row norms now, the packed f16 split at the first Gaussian launch: derived data, inside the step
-        last = run_classes(list(range(C)), True)
+        alphas = {} if args.dump_outputs else None          # class -> alpha of this step (references only: no copy, no sync)
+        last = run_classes(list(range(C)), True, alphas)
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -359,6 +378,7 @@ def main():
     health = {"failed_choleskys": int(hl[0].item()), "ranks_with_nonfinite_scores": int(hl[1].item()),
               "preconditioners_checked_rank0": len(infos)}
     healthy = health["failed_choleskys"] == 0 and health["ranks_with_nonfinite_scores"] == 0
+    dumped = dump_outputs(args.dump_outputs, alphas, scores, lo, seed) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         # Two kernel families, each with its own roofline object under a fixed key, compared family against family:
@@ -493,6 +513,8 @@ def main():
                                "collectives_replaced_by_local_copies_warmup_included": {k: {"calls": v[0], "bytes": v[1]} for k, v in shard.calls.items()},
                                "note": "value = N / this rank's compute-only step time: what the %d-rank job would reach if every rank took "
                                        "this long and the collectives were free; unmeasured on hardware" % args.emulate_world}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.check:
             out["check"] = check_against_oracle(be, F, last, X, row_ids, args, C - 1)
         want_cpu = not args.no_cpu_baseline and world == 1 and not emulated      # reported at N = 1 only
@@ -640,6 +662,25 @@ def cpu_baseline(args):
                       "in %.1f s; value = rows / (seconds x %d classes)%s" % (
                           ns, D, M, dt, args.classes,
                           "" if M == args.M else "; M reduced from %d to bound the O(M^3) host Cholesky" % args.M)}
+
+
+def dump_outputs(path, alphas, scores, row0, seed):
+    """--dump-outputs: what the last timed step handed back, as .npy files of DUMP_BUDGET_BYTES at most in all.
+    alpha.npy (classes, M) f64: every class's fitted coefficients.  scores.npy (rows, classes) f32: this rank's scores of the
+    rows listed in score_rows.npy (f64 global row indices, ascending): all of them when they fit the budget, else a sample
+    drawn with a fixed seed, so that two runs with the same arguments write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    A = np.stack([alphas[c].detach().double().cpu().numpy().reshape(-1) for c in sorted(alphas)])
+    n, C = scores.shape
+    room = DUMP_BUDGET_BYTES - A.nbytes - 3 * 4096            # (generous room for the three .npy headers)
+    cap = max(0, room // (4 * C + 8))
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+    S = scores.index_select(0, torch.from_numpy(rows).to(scores.device)).float().cpu().numpy()
+    files = {"alpha": A, "scores": S, "score_rows": (rows + row0).astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": {k: {"shape": list(a.shape), "dtype": str(a.dtype)} for k, a in files.items()},
+            "score_rows_sampled": bool(n > cap), "bytes": int(sum(a.nbytes for a in files.values()))}
 
 
 def check_against_oracle(be, F, last, X, row_ids, args, c):

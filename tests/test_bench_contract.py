@@ -119,3 +119,51 @@ def test_roofline_traffic_is_only_quoted_from_passes_of_this_trees_kernel_source
     json.dump({"csrc_sha16": sha}, open(prof / "r77_pmc_meta.json", "w"))
     got, why = bench.profiled_traffic_gb("knm_passq_stag_kernel<10,2,1>")
     assert got == 25.6 and sha in why
+
+
+def _load_bench(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_flag_checks():
+    """--dump-outputs is offered; --steps sets the timed step count, so fewer than one is refused before any GPU work."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--dump-outputs" in out.stdout
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and bad[0] in r.stderr
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: alpha (classes, M) f64 of every class in full; scores (rows, classes) f32 in full when they
+    fit, else on a sample of rows that is the same on every run (score_rows: their global row indices, f64), all files
+    together within the budget."""
+    import numpy as np
+    import torch
+    bench = _load_bench("bench_under_test3")
+    g = torch.Generator().manual_seed(0)
+    C, M, n, row0 = 5, 40, 3000, 1000
+    alphas = {c: torch.randn(M, dtype=torch.float64, generator=g) for c in reversed(range(C))}
+    scores = torch.randn(n, C, generator=g)
+    small = bench.dump_outputs(str(tmp_path / "full"), alphas, scores, row0, 7)
+    A, S, R = (np.load(str(tmp_path / "full" / (k + ".npy"))) for k in ("alpha", "scores", "score_rows"))
+    assert A.dtype == np.float64 and S.dtype == np.float32 and R.dtype == np.float64
+    assert np.array_equal(A, np.stack([alphas[c].numpy() for c in range(C)]))
+    assert np.array_equal(S, scores.numpy()) and np.array_equal(R, np.arange(row0, row0 + n)) and not small["score_rows_sampled"]
+    budget = A.nbytes + 3 * 4096 + 1000 * (4 * C + 8)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("sampled%d" % k)
+        info = bench.dump_outputs(str(d), alphas, scores, row0, 7)
+        assert info["score_rows_sampled"] and info["bytes"] <= budget
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= budget
+        runs.append([np.load(str(d / (k + ".npy"))) for k in ("alpha", "scores", "score_rows")])
+    A2, S2, R2 = runs[0]
+    assert S2.shape == (1000, C) and np.all(np.diff(R2) > 0)
+    assert np.array_equal(S2, scores.numpy()[(R2 - row0).astype(np.int64)]) and np.array_equal(A2, A)
+    assert all(np.array_equal(a, b) for a, b in zip(runs[0], runs[1]))

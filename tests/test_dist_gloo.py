@@ -20,6 +20,7 @@ def _free_port():
 
 
 def _worker(rank, world, port, n, ret):
+    torch.cuda.is_available = lambda: False      # the CPU path (oracle backend), also in a process that could see a GPU
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
@@ -185,6 +186,7 @@ def _train_minibootstrap(path, pos, neg, opts):
 
 
 def _class_shard_worker(rank, world, port, path, ret):
+    torch.cuda.is_available = lambda: False      # the CPU path (oracle backend), also in a process that could see a GPU
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
@@ -204,7 +206,7 @@ def _class_shard_worker(rank, world, port, path, ret):
 
 
 @pytest.mark.parametrize("world", [2, 3])
-def test_class_sharded_minibootstrap_equals_single_process(world, tmp_path):
+def test_class_sharded_minibootstrap_equals_single_process(world, tmp_path, monkeypatch):
     """opts['class_shard']: every rank trains the classes i % world == rank and ends with ALL models, bit for bit those of
     one process that gives each class its own RNG stream (opts['class_rng']); no rank trains another rank's classes."""
     import odx
@@ -213,6 +215,7 @@ def test_class_sharded_minibootstrap_equals_single_process(world, tmp_path):
     port = _free_port()
     ret = mp.Manager().dict()
     mp.spawn(_class_shard_worker, args=(world, port, path, ret), nprocs=world, join=True)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)      # the single process on the same CPU path as the ranks
     odx.set_backend(OracleBackend(np.float64))
     try:
         C, pos, neg = _minibootstrap_problem(path)

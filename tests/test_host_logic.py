@@ -242,7 +242,8 @@ class RidgeClassifier:
 
 
 @pytest.mark.parametrize("variant,modname", [("cpu", "OnlineRegionClassifier"), ("incore", "OnlineRegionClassifier_incore")])
-def test_minibootstrap_matches_reference_trace(variant, modname):
+def test_minibootstrap_matches_reference_trace(variant, modname, monkeypatch):
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)      # the golden trace is the CPU path's, GPU or not
     G = np.load(os.path.join(GOLD, "bootstrap_golden.npz"))
     mod = dropin.load(modname)
     C, ITER = int(G["C"]), int(G["ITER"])
@@ -445,40 +446,36 @@ def test_region_refiner_matches_reference(tag, is_rpn, tmp_path):
 
 
 # ------------------------------------------------------------------ INTEGRATION.md route 2
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/modules/region-classifier"),
-                    reason="reference checkout only exists in the build container")
-def test_reference_wrapper_runs_unchanged_on_odx_falkon(monkeypatch):
-    """sys.modules['falkon'] = odx.falkon: the REFERENCE's own FALKONWrapper (CPU variant) trains and
-    predicts through odx.  (CPU test, never runs on the GPU box.)"""
-    import sys
-    import types
+def test_reference_wrapper_calls_run_on_odx_falkon():
+    """odx.falkon in falkon's place: the calls the REFERENCE's own FALKONWrapper (CPU variant) makes into falkon,
+    as recorded from it (tests/golden/wrapper_contract.json, "cpu": its settings from cfg_bootstrap.yaml, the constructor's
+    keywords and options, fit on (n, D) rows with (n,) f32 labels, a centre selector whose select() returns the rows of its
+    indices as a tensor, predict), made on odx.falkon: the fit is the oracle's and predict has the reference's shape."""
     import odx.falkon
-    monkeypatch.setitem(sys.modules, "falkon", odx.falkon)
-    opts = types.ModuleType("falkon.options")
-    opts.FalkonOptions = odx.falkon.FalkonOptions
-    opts.__all__ = ["FalkonOptions"]
-    monkeypatch.setitem(sys.modules, "falkon.options", opts)
-    ref_dir = "/root/reference/src/modules/region-classifier"
-    src = open(os.path.join(ref_dir, "FALKONWrapper_with_centers_selection.py")).read()
-    mod = types.ModuleType("ref_wrapper_under_test")
-    mod.__file__ = os.path.join(ref_dir, "FALKONWrapper_with_centers_selection.py")
-    monkeypatch.syspath_prepend(ref_dir)
-    for name in ("ClassifierAbstract", "MyCenterSelector"):
-        monkeypatch.delitem(sys.modules, name, raising=False)
-    exec(compile(src, mod.__file__, "exec"), mod.__dict__)
-    for name in ("ClassifierAbstract", "MyCenterSelector"):
-        sys.modules.pop(name, None)
-    w = mod.FALKONWrapper(cfg_path=os.path.join(GOLD, "cfg_bootstrap.yaml"))
+    contract = json.load(open(os.path.join(GOLD, "wrapper_contract.json")))["cpu"]
+    attrs, ctor = contract["attrs"], contract["record"]["ctor"][0]
+
+    class RowsOfIndices:                      # what the reference's MyCenterSelector.select hands back (contract "select")
+        def __init__(self, indices):
+            self.indices = indices
+
+        def select(self, X, Y):
+            return X[self.indices]
+
     X, y, rng = blob_problem(300, 16, seed=4)
     Xt, yt = torch.from_numpy(X), torch.from_numpy(y)
+    assert contract["record"]["fit"][0]["y_dtype"] == str(yt.dtype) and len(contract["record"]["fit"][0]["y"]) == yt.dim()
     torch.manual_seed(3)
-    model = quiet(w.train, Xt, yt)
-    torch.manual_seed(3)
-    idx = fr.compute_indices_selection(y, 40, lambda high, size: torch.randint(high, (size,)).numpy())
+    idx = fr.compute_indices_selection(y, attrs["nyst_centers"], lambda high, size: torch.randint(high, (size,)).numpy())
+    kw = {"kernel": odx.falkon.GaussianKernel(attrs["sigma"]), "penalty": attrs["lam"], "M": attrs["nyst_centers"],
+          "center_selection": RowsOfIndices(idx), "options": odx.falkon.FalkonOptions(**ctor["options"])}
+    assert sorted(kw) == sorted(ctor) and attrs["maxiter"] is None        # (no maxiter keyword: falkon's default)
+    model = odx.falkon.Falkon(**kw)
+    model.fit(Xt, yt)
     ref, Z = fr.falkon_fit(X.astype(np.float64), y, idx, 10.0, 1e-3, maxiter=20, dtype=np.float64, pc_eps=1e-5, cg_epsilon=1e-7)
     assert np.linalg.norm(model.alpha_.numpy() - ref) / np.linalg.norm(ref) < 1e-6
-    p = w.predict(model, Xt[:6])
-    assert tuple(p.shape) == (6, 1)
+    p = model.predict(Xt[:6])
+    assert tuple(p.shape) == (6, contract["predict_shape"][1])
 
 
 # ------------------------------------------------------------------ test-time heads (A8 / A9)

@@ -177,10 +177,11 @@ def test_segmentation_ap_matches_reference():
         np.testing.assert_allclose(r["ap"], MG["seg_ap_%s" % ("voc07" if m07 else "area")], atol=1e-12, equal_nan=True)
 
 
-def test_standalone_accuracy_evaluator_dropin(tmp_path):
+def test_standalone_accuracy_evaluator_dropin(tmp_path, monkeypatch):
     """`import AccuracyEvaluator as ae` (the stand-alone O-OD evaluator of the reference): post-processing of the
     per-image BoxLists that testRegionClassifier / RegionRefiner.predict leave, then the reference's AP — on the golden
     post-processing case its kept detections are the reference's, and detections equal to the ground truth score AP 1."""
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)      # the oracle backend's CPU path, GPU or not
     import yaml
     from odx.boxlist import BoxList
     from tests import dropin

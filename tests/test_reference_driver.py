@@ -7,7 +7,6 @@ and run as __main__, not a line changed — left in its output directory when ru
 `--load_RPN_detector_segmentation_features --save_RPN_detector_segmentation_models --CPU`: the three classifier / regressor /
 stats model files (structure, shapes, norms, leading values) and the mAP lines of result.txt.
 
-  * where /root/reference exists (this container): the driver is executed again and must leave exactly that;
   * everywhere: the same call sequence restated on the drop-in modules (tests/driver_fixture.replay) leaves exactly that on
     the CPU (f64 oracle backend) — the restatement IS the driver's sequence —, and
   * on the MI355X (libodx): the same models to the north star's tolerances — alphas 1e-4 relative, mAP within 0.1."""
@@ -58,23 +57,6 @@ def _close(got, want, rtol, path=""):
 
 def _maps(lines):
     return {m.group(1): float(m.group(2)) for l in lines for m in [re.match(r"(\w+) mAP50: ([0-9.]+|nan)", l)] if m}
-
-
-@pytest.mark.skipif(not os.path.exists(df.REF_DRIVER), reason="the reference is only present in the build container")
-def test_reference_driver_runs_unchanged_on_the_dropins(tmp_path, monkeypatch):
-    from tests.golden.make_driver_golden import run_reference_driver
-    from tests.oracle_backend import OracleBackend
-    odx.set_backend(OracleBackend(np.float64))
-    try:
-        out, cfg_path, want = _setup(tmp_path, "cpu")
-        run_reference_driver(out, cfg_path)                     # experiments/run_experiment_online_rpn_ood_oos.py, unmodified
-        got = df.summarize(out)
-        _close(got, want, 1e-9)
-        assert got["files"] == ["cfg.yaml", "classifier_detector", "classifier_rpn", "classifier_segmentation", "regressor_detector",
-                                "regressor_rpn", "result.txt", "stats_detector", "stats_rpn", "stats_segmentation"]
-        assert set(_maps(got["result_lines"])) == {"Detection", "Segmentation"}
-    finally:
-        odx.set_backend(None)
 
 
 def test_restated_call_sequence_leaves_what_the_driver_left_cpu(tmp_path):
