@@ -222,6 +222,13 @@ int64_t odx_knm_fwd_bwd2_q_workspace_bytes(int64_t n, int64_t M, int fmt);
 int odx_knm_fwd_bwd2_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
                        const double* v, const double* v2, double* out, double* out2, void* workspace,
                        int64_t workspace_bytes, odx_stream_t stream);
+/* out[r * ldo] = (float) sum_j K[r, j] alpha[j], r < n, over a stored block in any of the three formats (scores from the
+ * block a fit streamed: one read of it instead of a second Gaussian contraction).  Accumulated in f64 in a fixed order
+ * (bitwise reproducible); no workspace.  M <= 20476; ldk (and ldlo for ODX_KNM_U24) a multiple of 4, >= roundup(M, 4);
+ * K 16-byte (f32) / 8-byte aligned, Klo 4-byte aligned; columns [M, roundup(M, 4)) must hold finite values (the builds
+ * write zeros).  Row sub-blocks of a stored shard are valid arguments. */
+int odx_knm_mv(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, const double* alpha,
+               float* out, int64_t ldo, odx_stream_t stream);
 
 /* ---------------------------------------------------------------- A3 / A5 with the fp8 contraction (BASELINE config 5)
  * "fp8 (OCP e4m3) inputs to the X Z' MFMA, f32 accumulate, stress / throughput only" (cfg 5; the reference's own

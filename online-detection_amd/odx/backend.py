@@ -658,6 +658,20 @@ class HipBackend:
         hip.check(self.lib.odx_axpby_f64(float(a), _p(x), float(b), _p(y), y.numel(), self._stream()), "odx_axpby_f64")
 
     # ------------------------------------------------------------------ scoring
+    def knm_mv(self, K, alpha, out=None):
+        """(n, 1) f32 = K alpha over a stored K_nM block, from one read of it (odx_knm_mv; f64 sums); `out` may be a
+        strided column such as scores[:, c:c + 1]."""
+        alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
+        if alpha.numel() != K.M:
+            raise ValueError("knm_mv: alpha has %d entries but the block has %d columns" % (alpha.numel(), K.M))
+        if out is None:
+            out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or out.shape[0] != K.n or (out.dim() == 2 and out.shape[1] != 1):
+            raise ValueError("knm_mv: out must be an (n,) or (n, 1) f32 tensor")
+        hip.check(self.lib.odx_knm_mv(_p(K.K), K.ld, _p(K.lo), K.ld, _KNM_CODE[K.fmt], K.n, K.M, _p(alpha), _p(out),
+                                      out.stride(0), self._stream()), "odx_knm_mv")
+        return out
+
     def mmv(self, F, Zf, sigma, V, ranges=None, out=None, max_range=None):
         """(n, T) f32 = K(F, Zf) @ V with V (Mtot, T) f64; ``ranges`` (T, 2) int32 row ranges of the
         non-zero block of each column (None = dense); ``max_range``: an upper bound of the range lengths when the

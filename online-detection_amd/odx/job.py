@@ -96,14 +96,17 @@ class LockstepClassJob:
 
     def __init__(self, be, X, n_total, M, labels, centre_idx, sigma, lam, maxiter=20, opt=None, shard=None,
                  precond_batch=0, precond_depth=2, precond_after_fit=False, classes=None, precond_cus=0, batch=0,
-                 hbm_bytes=None, exchange="lockstep", gauss_on_complement=False, precond_lookahead=1, precond_cus_full_only=False):
+                 hbm_bytes=None, exchange="lockstep", gauss_on_complement=False, precond_lookahead=1, precond_cus_full_only=False,
+                 score_from_knm=True):
         """precond_batch: classes per rank and preconditioner chain (g; 0 = planned, 1 = one chain per class on `precond_depth`
         side streams); batch: classes per lock-step batch (b, a divisor of the world size; 0 = planned); hbm_bytes: the
         memory the plan may count on per rank (default: the device's, 288 GB without one).
         exchange: "lockstep" — batches of b classes, one owner rank per class, per CG iteration one all-gather of the
         directions and one reduce-scatter of the partials (what bench.py times); "allreduce" — the north star's literal form:
         classes one at a time, EVERY rank builds every class's preconditioner and runs every M-sized product, per CG iteration
-        ONE all-reduce of the (M,) partial (solver.falkon_fit's replicated mode).  Same arithmetic per class either way."""
+        ONE all-reduce of the (M,) partial (solver.falkon_fit's replicated mode).  Same arithmetic per class either way.
+        score_from_knm: score a class from the K_nM shard its fit has just stored (one read of it, backend.knm_mv) where
+        that shard holds the f32-accurate entries (see _score); False: always recompute K(X, Z) alpha (backend.mmv)."""
         # gauss_on_complement (with precond_cus = k > 0; an experiment, round-5 review item 1a): the K_nM builds and the scoring run
         # on a stream confined to the OTHER total - k compute units, so that chain and Gaussian workgroups never share a CU.
         # precond_lookahead = L: chain groups in flight ahead of the group being fitted (L + 1 factor blocks; 1 = round 2-5's
@@ -114,6 +117,7 @@ class LockstepClassJob:
         if exchange not in ("lockstep", "allreduce"):
             raise ValueError("LockstepClassJob: exchange must be 'lockstep' or 'allreduce', got %r" % (exchange,))
         self.exchange = exchange
+        self.score_from_knm = bool(score_from_knm)
         if exchange == "allreduce":
             batch = 1                             # one stored K_nM shard in flight; the plan's b = 1 line is this mode's memory
         self.be, self.X, self.N, self.M = be, X, int(n_total), int(M)
@@ -229,6 +233,21 @@ class LockstepClassJob:
         self.shard.gather_blocks(blk, allb)
         return be.features(allb.view(self.world * cmax, X.shape[1]).index_select(0, slot))
 
+    def _score(self, ph, F, Z, K, alpha, c):
+        """scores[:, c] = K(X, Z) alpha.  From the stored shard K the fit has just streamed when its entries are the Gaussian's
+        f32-accurate values (gauss "h2", stored as 24-bit fixed point or f32): one HBM-bound read of it, timed with the passes
+        ("ktk"), instead of a second 2 n M D contraction.  bf16 / f8 shards are ~1e-3 off, so their scores (and those of a
+        backend without knm_mv) are recomputed by the contraction.  The next batch's build overwrites K only after this
+        launch, in stream order."""
+        be = self.be
+        if (self.score_from_knm and K is not None and hasattr(be, "knm_mv") and getattr(be, "gauss", None) == "h2"
+                and getattr(K, "fmt", None) in ("u24", "f32")):
+            with ph("ktk"):
+                be.knm_mv(K, alpha, out=self.scores[:, c:c + 1])
+        else:
+            with ph("mmv"):
+                be.mmv(F, Z, self.sigma, alpha, None, out=self.scores[:, c:c + 1])
+
     def _prepare(self, batch, owners, slot, ph, infos):
         """Per-class mode (G == 1): centres of the batch's classes (one all-reduce each, main stream) and, on the slot's side
         stream, the preconditioner of the class this rank owns in the batch."""
@@ -320,14 +339,14 @@ class LockstepClassJob:
                 ready.update(prepare(gi + 1))
             Z, P, ev = ready.pop(c)
             self.trace.append(("fit", (c,)))
+            Ks = []
             alpha = solver.falkon_fit(be, F, self.labels(c), Z, self.sigma, self.lam, self.maxiter, self.opt, n_total=self.N,
                                       shard=self.shard, owner=None, knm_out=self.kbufs[0],
                                       phase=(lambda name: phases[name]) if phases is not None else None,
-                                      precond=P, precond_ready=(lambda ev=ev: _wait(ev)))
+                                      precond=P, precond_ready=(lambda ev=ev: _wait(ev)), knm_blocks=Ks)
             if alphas_out is not None:
                 alphas_out[c] = alpha
-            with ph("mmv"):
-                be.mmv(F, Z, self.sigma, alpha, None, out=self.scores[:, c:c + 1])
+            self._score(ph, F, Z, Ks[0] if Ks else None, alpha, c)
             out = (alpha, Z)
         if hasattr(be, "release_helper_streams"):
             be.release_helper_streams()
@@ -373,11 +392,12 @@ class LockstepClassJob:
             ys = [self.labels(c) for c in batch]
             mine = rank in owners
             self.trace.append(("fit", tuple(batch)))
+            Ks = []
             alphas = solver.falkon_fit_lockstep(be, F, ys, Zs, self.sigma, self.lam, self.maxiter, self.opt, n_total=self.N,
                                                 shard=self.shard, knm_outs=self.kbufs[:len(batch)],
                                                 phase=ph if (phases is not None or self.gauss_stream is not None) else None,
                                                 precond=P if mine else None,
-                                                precond_ready=(lambda: _wait(ev)) if mine else None, owners=owners)
+                                                precond_ready=(lambda: _wait(ev)) if mine else None, owners=owners, knm_blocks=Ks)
             if self.G == 1 and self.after_fit and bi + self.depth < len(sched):
                 # issued behind this batch's CG in stream order: the factorisations then run beside the MFMA-bound scoring
                 # of this batch and K_nM build of the next, and the HBM-bound passes keep the chip to themselves
@@ -385,8 +405,7 @@ class LockstepClassJob:
             if alphas_out is not None:
                 alphas_out.update((c, alphas[pos]) for pos, c in enumerate(batch))
             for pos, c in enumerate(batch):
-                with ph("mmv"):
-                    be.mmv(F, Zs[pos], self.sigma, alphas[pos], None, out=self.scores[:, c:c + 1])
+                self._score(ph, F, Zs[pos], Ks[pos] if pos < len(Ks) else None, alphas[pos], c)
             out = (alphas[-1], Zs[-1])
         if hasattr(be, "release_helper_streams"):
             # the chains' internal helper streams go when the step is queued (their work completes first; the next step's first

@@ -74,7 +74,7 @@ def _can_fold(be, K, M, rows_per_rank):
 
 
 def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, allreduce=None, knm_out=None,
-               return_knm=False, phase=None, precond=None, shard=None, owner=None, precond_ready=None):
+               return_knm=False, phase=None, precond=None, shard=None, owner=None, precond_ready=None, knm_blocks=None):
     """Fit one binary FALKON problem.
 
     be        backend (odx.backend.HipBackend in the product)
@@ -100,6 +100,9 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
               optional callable invoked once, right before the preconditioner is first applied
               (after the K_nM build and the right-hand-side pass were issued): lets a preconditioner
               that is still being computed on another stream overlap with them
+    knm_blocks
+              optional list that receives the K_nM block this fit built (the stored shard its passes
+              streamed: the caller can score from it)
     returns   alpha (M,) f64 device vector (on every rank)
     """
     opt = opt or SolverOptions()
@@ -119,6 +122,8 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     yn = y * (1.0 / n)
     with ph("knm"):
         K, b0 = be.knm_rhs(F, Zf, sigma, yn, out=knm_out)   # K_nM and this shard's K' (y / n), out of the same launch
+    if knm_blocks is not None:
+        knm_blocks.append(K)
 
     def ktk(**kw):
         with ph("ktk"):
@@ -237,7 +242,7 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
 
 
 def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_total=None, shard=None, knm_outs=None,
-                        phase=None, precond=None, precond_ready=None, owners=None):
+                        phase=None, precond=None, precond_ready=None, owners=None, knm_blocks=None):
     """Fit up to `world` binary problems at once over row shards, one owner rank per problem.
 
     Problem b (labels ys[b], centres Zfs[b]) is owned by rank owners[b] (default: rank b): only that rank holds its
@@ -252,6 +257,7 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
 
     ys, Zfs     lists of B <= world label vectors / centre Features (identical on every rank)
     knm_outs    optional list of B preallocated f32 buffers for the K_nM shards
+    knm_blocks  optional list that receives the B K_nM shards built here, in problem order
     precond     this rank's problem's preconditioner (when it owns one), or None to build it here
     returns     list of B alpha vectors (M,) f64, on every rank
     """
@@ -283,6 +289,8 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         with ph("knm"):                               # K_nM shard and this shard's K' (y / n) of problem b in one launch
             Ks.append(be.knm_rhs(F, Zfs[b], sigma, ys[b] * (1.0 / n), out=None if knm_outs is None else knm_outs[b],
                                  rhs_out=CC[owners[b], :M])[0])
+    if knm_blocks is not None:
+        knm_blocks.extend(Ks)
     tbuf, ccbuf, v = be.zeros(Mp), be.zeros(Mp), be.zeros(M)
     t, cc = tbuf[:M], ccbuf[:M]
 
