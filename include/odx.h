@@ -229,6 +229,20 @@ int odx_knm_fwd_bwd2_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo
  * write zeros).  Row sub-blocks of a stored shard are valid arguments. */
 int odx_knm_mv(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, const double* alpha,
                float* out, int64_t ldo, odx_stream_t stream);
+/* The CG pass over a shard whose K_nM is NEVER stored (option knm_storage "stream"): out = K' (K v + w) and, when v2 is given,
+ * out2 = K' (K v2), with K = K(X, Z) recomputed on the split-f16 tile core for every call.  Arguments as odx_gauss_knm_h2_store
+ * (packed operands of odx_split_f16, their meta and squared norms); v, v2 (M) f64 or NULL, w (n) f64 or NULL, out / out2 (M)
+ * f64.  v = w = NULL gives out = 0.  Rows go through a ring of odx_gauss_ktk_stream_h2_rows(M, D) rows inside `workspace`:
+ * each chunk is built by odx_gauss_knm_h2_store in ODX_KNM_U24 — entries bit-identical to a stored 24-bit block of the same
+ * shard — and read back by odx_knm_fwd_bwd_q / odx_knm_fwd_bwd2_q while it is resident in the Infinity Cache; the chunks'
+ * vectors are added in row order (f64, fixed order, bitwise reproducible).  M <= 20440 (ODX_ERR_UNSUPPORTED above); the
+ * workspace does not grow with n. */
+int64_t odx_gauss_ktk_stream_h2_rows(int64_t M, int D);
+int64_t odx_gauss_ktk_stream_h2_workspace_bytes(int64_t n, int64_t M, int D);
+int odx_gauss_ktk_stream_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                            const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                            double sigma, const double* v, const double* v2, const double* w, double* out, double* out2,
+                            void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 /* ---------------------------------------------------------------- A3 / A5 with the fp8 contraction (BASELINE config 5)
  * "fp8 (OCP e4m3) inputs to the X Z' MFMA, f32 accumulate, stress / throughput only" (cfg 5; the reference's own

@@ -95,6 +95,18 @@ class Knm:
         return sub
 
 
+class KnmStream:
+    """A K_nM shard that is NEVER stored (knm_storage "stream"): the rows F, the centres Zf and sigma, from which every pass
+    (ktk / ktk2) recomputes K chunk by chunk into a ring (odx_gauss_ktk_stream_h2).  ring: the caller's buffer for it (a
+    LockstepClassJob's per-batch K buffer) or None for the backend's per-stream workspace.  K: the packed rows the passes read
+    (what record_stream is asked about)."""
+    __slots__ = ("F", "Zf", "sigma", "n", "M", "ring", "K", "fmt", "lo")
+
+    def __init__(self, F, Zf, sigma, ring=None):
+        self.F, self.Zf, self.sigma, self.n, self.M, self.ring = F, Zf, float(sigma), F.n, Zf.n, ring
+        self.K, self.fmt, self.lo = F.P, "stream", None
+
+
 _KNM_CODE = {"f32": hip.KNM_F32, "u24": hip.KNM_U24, "bf16": hip.KNM_BF16}
 
 
@@ -400,7 +412,13 @@ class HipBackend:
             raise hip.OdxError("FALKON preconditioner: non-positive pivot at index %d (Cholesky failed)" % (info - 1))
 
     def knm_format(self, n, M):
-        """Storage format a K_nM block of this shape gets (see __init__)."""
+        """Storage format a K_nM block of this shape gets (see __init__); "stream" under knm_storage "stream" (no block at all:
+        knm_rhs hands out a KnmStream), which only the split-f16 kernels have."""
+        if self.knm_storage == "stream":
+            if self.gauss != "h2":
+                raise ValueError("knm_storage 'stream' needs gauss 'h2' (the streamed pass recomputes K on the split-f16 tile core); "
+                                 "gauss is %r" % (self.gauss,))
+            return "stream"
         if self.gauss not in ("h2", "f8") or n <= 0 or M <= 0:
             return "f32"
         if self.knm_storage in ("u24", "bf16"):
@@ -410,9 +428,19 @@ class HipBackend:
             return "u24"
         return "f32"
 
-    def knm_bytes(self, n, M):
-        """Bytes of the K_nM block knm() / knm_rhs() make for this shape (for preallocated `out` buffers)."""
+    def knm_bytes(self, n, M, D=None):
+        """Bytes of the K_nM block knm() / knm_rhs() make for this shape (for preallocated `out` buffers).  Streamed: the
+        ring and the workspace of its passes for D features (the largest ring, that of D = 64, when D is not given), which do
+        not grow with n."""
+        if self.knm_format(n, M) == "stream":
+            return max(0, int(self._stream_bytes(max(n, 1), M, 64 if D is None else D)))
         return int(self.lib.odx_knm_bytes(max(n, 0), M, _KNM_CODE[self.knm_format(n, M)]))
+
+    def _stream_bytes(self, n, M, D):
+        nbytes = int(self.lib.odx_gauss_ktk_stream_h2_workspace_bytes(n, M, D))
+        if nbytes < 0:
+            raise hip.OdxError("odx_gauss_ktk_stream_h2: M = %d is outside the supported range (M <= 20440)" % M)
+        return nbytes
 
     def _knm_block(self, n, M, fmt, out):
         K = Knm()
@@ -437,6 +465,8 @@ class HipBackend:
     def knm(self, F, Zf, sigma, out=None):
         n, M = F.n, Zf.n
         fmt = self.knm_format(n, M)
+        if fmt == "stream":
+            raise ValueError("knm: knm_storage 'stream' stores no K_nM block (knm_rhs hands out a streamed shard)")
         if fmt != "f32" or self.gauss == "f8":
             return self._knm_store(F, Zf, sigma, fmt, None, out, None)[0]
         K = self._knm_block(n, M, "f32", out)
@@ -495,6 +525,17 @@ class HipBackend:
         if rhs_out is None:
             rhs_out = torch.empty(M, dtype=torch.float64, device=self.device)
         fmt = self.knm_format(n, M)
+        if fmt == "stream":
+            # no block: a handle from which every pass recomputes K; b0 = K' w is one streamed pass (v = 0)
+            self.pack(F), self.pack(Zf)
+            ring = None
+            if out is not None:
+                raw = out.view(-1).view(torch.uint8)
+                if raw.numel() >= self._stream_bytes(max(n, 1), M, F.D) and raw.data_ptr() % 16 == 0:
+                    ring = raw
+            K = KnmStream(F, Zf, sigma, ring)
+            w = None if w is None else w.to(dtype=torch.float64, device=self.device).contiguous()
+            return K, self.ktk(K, w=w, out=rhs_out)
         if (fmt != "f32" or self.gauss == "f8") and n > 0:
             return self._knm_store(F, Zf, sigma, fmt, w, out, rhs_out)
         if not (self.gauss == "h2" and n > 0 and self.lib.odx_gauss_h2_tile(n, M) == 256) or self.direct_small(n, M, F.D):
@@ -511,10 +552,22 @@ class HipBackend:
         """Leave `cus` CUs free while the persistent CG pass kernel runs, for work queued on other streams."""
         hip.check(self.lib.odx_set_pass_reserved_cus(int(cus)), "odx_set_pass_reserved_cus")
 
+    def _ktk_stream(self, K, v, v2, w, out, out2):
+        """out = K' (K v + w) [, out2 = K' (K v2)] with K recomputed chunk by chunk (odx_gauss_ktk_stream_h2)."""
+        F, Zf = K.F, K.Zf
+        nbytes = self._stream_bytes(max(K.n, 1), K.M, F.D)
+        ws = K.ring if K.ring is not None else self._workspace("ktk_stream", nbytes)
+        hip.check(self.lib.odx_gauss_ktk_stream_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), K.n, _p(Zf.P), Zf.P.stride(0),
+                                                   _p(Zf.meta), _p(Zf.sq), K.M, F.D, K.sigma, _p(v), _p(v2), _p(w), _p(out),
+                                                   _p(out2), _p(ws), ws.numel(), self._stream()), "odx_gauss_ktk_stream_h2")
+
     def ktk(self, K, v=None, w=None, out=None):
         """out = K' (K v + w) over this shard (f64)."""
         if out is None:
             out = torch.empty(K.M, dtype=torch.float64, device=self.device)
+        if K.fmt == "stream":
+            self._ktk_stream(K, v, None, w, out, None)
+            return out
         if K.fmt != "f32":
             code = _KNM_CODE[K.fmt]
             nbytes = self.lib.odx_knm_fwd_bwd_q_workspace_bytes(max(K.n, 1), K.M, code)
@@ -538,8 +591,9 @@ class HipBackend:
         return self.lib.odx_knm_fwd_bwd2_workspace_bytes(max(K.n, 1), K.M)
 
     def can_ktk2(self, K):
-        """Whether the two-vector pass exists at this block's width (both vectors must fit in LDS: M <= 10 000)."""
-        return self._ktk2_bytes(K) >= 0
+        """Whether the two-vector pass exists at this block's width (both vectors must fit in LDS: M <= 10 000).  A streamed
+        shard always has one: each chunk is built once and read for both vectors while it is resident."""
+        return K.fmt == "stream" or self._ktk2_bytes(K) >= 0
 
     def ktk2(self, K, v1, v2, out1=None, out2=None):
         """out1 = K' (K v1), out2 = K' (K v2) over this shard from ONE read of K (odx_knm_fwd_bwd2[_q])."""
@@ -547,6 +601,9 @@ class HipBackend:
             out1 = torch.empty(K.M, dtype=torch.float64, device=self.device)
         if out2 is None:
             out2 = torch.empty(K.M, dtype=torch.float64, device=self.device)
+        if K.fmt == "stream":
+            self._ktk_stream(K, v1, v2, None, out1, out2)
+            return out1, out2
         nbytes = self._ktk2_bytes(K)
         if nbytes < 0:
             raise hip.OdxError("odx_knm_fwd_bwd2: M = %d is outside the two-vector configurations" % K.M)
@@ -583,7 +640,7 @@ class HipBackend:
         """Whether cg_solve_batched has a lock-step loop for blocks of these shapes stored as `fmt` (one pass configuration
         for all of them) — asked BEFORE the blocks are built."""
         B = len(ns)
-        if not 1 <= B <= self.MAX_CLASS_BATCH:
+        if not 1 <= B <= self.MAX_CLASS_BATCH or fmt == "stream":       # (the library loops stream stored blocks only)
             return False
         n = (ctypes.c_int64 * B)(*[int(v) for v in ns])
         M = (ctypes.c_int64 * B)(*[int(v) for v in Ms])
@@ -599,7 +656,7 @@ class HipBackend:
         a compact format (24-bit fixed point, bf16) go through odx_falkon_cg_batched_q_f64."""
         B = len(Ks)
         fmt = Ks[0].fmt
-        if any(k.fmt != fmt for k in Ks):           # one storage format per batch
+        if fmt == "stream" or any(k.fmt != fmt for k in Ks):     # one stored format per batch
             return None
         n = (ctypes.c_int64 * B)(*[int(k.n) for k in Ks])
         M = (ctypes.c_int64 * B)(*[int(k.M) for k in Ks])
@@ -661,6 +718,8 @@ class HipBackend:
     def knm_mv(self, K, alpha, out=None):
         """(n, 1) f32 = K alpha over a stored K_nM block, from one read of it (odx_knm_mv; f64 sums); `out` may be a
         strided column such as scores[:, c:c + 1]."""
+        if K.fmt not in _KNM_CODE:
+            raise ValueError("knm_mv: needs a stored K_nM block, got %r (a streamed shard is scored by mmv)" % (K.fmt,))
         alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
         if alpha.numel() != K.M:
             raise ValueError("knm_mv: alpha has %d entries but the block has %d columns" % (alpha.numel(), K.M))

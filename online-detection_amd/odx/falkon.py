@@ -28,7 +28,8 @@ class FalkonOptions:
     (pc_epsilon_32, cg_epsilon_32, cg_tolerance, cg_full_gradient_every); the memory /
     dispatch knobs the reference passes (min_cuda_iter_size_*, min_cuda_pc_size_*,
     keops_active, store_kernel_d_threshold — FALKONWrapper_..._incore.py:56) have nothing to
-    select here: K_nM is always materialised on the GPU and nothing runs on the CPU."""
+    select here: K_nM is materialised on the GPU (or, under the option knm_storage = "stream", recomputed by every CG pass
+    through a ring in the Infinity Cache) and nothing runs on the CPU."""
 
     def __init__(self, **kw):
         self.pc_epsilon_32 = kw.pop("pc_epsilon_32", 1e-5)

@@ -144,7 +144,9 @@ class LockstepClassJob:
             raise MemoryError("LockstepClassJob: this job does not fit %d rank(s): %s" % (self.world, self.plan.summary()))
         self.b, self.G = self.plan.b, self.plan.g
         self.R = self.world // self.b                   # batches per round (every rank owns one class per round)
-        kbytes = be.knm_bytes(self.n_loc, self.M) if hasattr(be, "knm_bytes") else self.n_loc * self.ldk * 4
+        # (streamed shards, knm_storage "stream": each buffer is the ring of a class's streamed passes, not a block)
+        kbytes = (be.knm_bytes(self.n_loc, self.M, D) if self.plan.knm_format == "stream" else be.knm_bytes(self.n_loc, self.M)) \
+            if hasattr(be, "knm_bytes") else self.n_loc * self.ldk * 4
         self.kbufs = [torch.empty(max(kbytes, 16), dtype=torch.uint8, device=dev) for _ in range(self.b)]
         self.scores = torch.empty((self.n_loc, self.C), dtype=torch.float32, device=dev)
         self.depth = precond_depth if precond_depth > 0 else 2

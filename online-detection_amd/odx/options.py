@@ -21,7 +21,8 @@ class Options:
     gauss: str = "h2"                # "h2": X Z' on the f16 matrix cores via the two-term split (f32 accuracy) | "f32": all-f32 MFMA
     #                                  | "f8": BASELINE config 5's e4m3 contraction (throughput only)
     knm_storage: str = "auto"        # stored K_nM: "auto" (24-bit fixed point where the passes are HBM-bound, f32 below) | "f32" | "u24"
-    #                                  | "bf16" (config 2's throughput-only storage)
+    #                                  | "bf16" (config 2's throughput-only storage) | "stream": never stored, every CG pass recomputes
+    #                                  K through a ring in the Infinity Cache (gauss "h2" only; for shards larger than HBM)
     precond: str = "auto"            # A factor of the preconditioner on the split-f16 core: "auto" (from 4096 centres on) | "f64" | "split"
     h2_tile: int = 0                 # tile core of the split kernels: 0 automatic | 128 | 256
     chain_helpers: int = -1          # helper streams of the factorisation chains: -1 automatic (from 4096 rows on) | 0 | 1
@@ -50,7 +51,7 @@ ENV = {
     "ODX_REFERENCE_ORDER": "reference_order", "ODX_CLASS_SHARD": "class_shard",
 }
 
-_CHOICES = {"gauss": ("h2", "f32", "f8"), "knm_storage": ("auto", "f32", "u24", "bf16"), "precond": ("auto", "f64", "split"),
+_CHOICES = {"gauss": ("h2", "f32", "f8"), "knm_storage": ("auto", "f32", "u24", "bf16", "stream"), "precond": ("auto", "f64", "split"),
             "h2_tile": (0, 128, 256), "chain_helpers": (-1, 0, 1), "trunk": ("rows", "conv"), "stream_probe": ("host", "events"),
             "reference_order": ("auto", "sequential")}
 _PRECOND_CODE = {"auto": 0, "f64": 1, "split": 2}

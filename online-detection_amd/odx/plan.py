@@ -28,10 +28,16 @@ def _round_up(x, m):
     return (int(x) + m - 1) // m * m
 
 
+# what a streamed shard (knm_storage "stream") holds instead of its block: the ring and its passes' workspace, sized in
+# csrc/knm_stream.hip to stay inside the 256 MiB Infinity Cache whatever n is
+STREAM_BYTES = 256 << 20
+
+
 def knm_format_rule(n, M, storage="auto", wide_tile=True):
     """The storage format HipBackend.knm_format gives an (n, M) block (tests/test_gpu_modules.py compares the two): 24-bit
-    fixed point where the passes are HBM-bound (>= 2^27 entries, at least 1024 centres, the wide tile core), f32 below."""
-    if storage in ("f32", "u24", "bf16"):
+    fixed point where the passes are HBM-bound (>= 2^27 entries, at least 1024 centres, the wide tile core), f32 below;
+    "stream" (no block) only when asked for — "auto" never streams."""
+    if storage in ("f32", "u24", "bf16", "stream"):
         return storage
     if n * M >= (1 << 27) and M >= 1024 and wide_tile:
         return "u24"
@@ -40,7 +46,9 @@ def knm_format_rule(n, M, storage="auto", wide_tile=True):
 
 def knm_bytes_rule(n, M, fmt):
     """Bytes of a stored (n, M) block: f32 rows of roundup(M, 4) floats; the compact formats planes of roundup(M, 8)
-    entries, 3 (u16 + u8 planes) or 2 (bf16) bytes each (include/odx.h, odx_knm_bytes)."""
+    entries, 3 (u16 + u8 planes) or 2 (bf16) bytes each (include/odx.h, odx_knm_bytes).  A streamed shard: its ring."""
+    if fmt == "stream":
+        return STREAM_BYTES
     if fmt == "f32":
         return int(n) * _round_up(M, 4) * 4
     return int(n) * _round_up(M, 8) * (3 if fmt == "u24" else 2)

@@ -68,9 +68,12 @@ class _NoPhase:
 
 def _can_fold(be, K, M, rows_per_rank):
     """The two-vector pass exists for this block width and pays for itself: a pass reads 4 n M bytes, the second vector's
-    four extra triangular products 16 M^2.  Decided from quantities every rank agrees on (M and the job's rows per rank),
-    never from the local shard length, so that all ranks issue the same collectives."""
-    return bool(hasattr(be, "ktk2") and be.can_ktk2(K) and rows_per_rank >= 8 * M)
+    four extra triangular products 16 M^2.  Decided from quantities every rank agrees on (M, the job's rows per rank and the
+    storage option), never from the local shard length, so that all ranks issue the same collectives.  A streamed shard
+    (K recomputed by every pass, 2 n M D flop) always folds."""
+    if not (hasattr(be, "ktk2") and be.can_ktk2(K)):
+        return False
+    return bool(getattr(K, "fmt", None) == "stream" or rows_per_rank >= 8 * M)
 
 
 def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, allreduce=None, knm_out=None,
@@ -154,6 +157,7 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     else:
         can_fold = allreduce is None and _can_fold(be, K, M, int(n))
     tt2 = be.zeros(2 * ((M + 1) // 2 * 2)).view(2, -1) if can_fold else None
+    cc2 = be.zeros(2 * ((M + 1) // 2 * 2)).view(2, -1) if can_fold else None     # (rows 16-byte aligned for odd M too)
     v2 = be.zeros(M) if can_fold else None
 
     def mmv2(s1, out1, s2, out2):
@@ -166,13 +170,12 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
             be.trmv(P, "LTit", v2, out=t2)
         bcast(tt2)
         with ph("ktk2"):
-            c1, c2 = be.ktk2(K, t1, t2)
-        cc2 = torch.stack((c1, c2))
+            be.ktk2(K, t1, t2, out1=cc2[0, :M], out2=cc2[1, :M])
         ar(cc2)
         if owned:
-            u = be.trmv(P, "LTi", cc2[0], alpha=1.0 / n, beta=lam, z=v)
+            u = be.trmv(P, "LTi", cc2[0, :M], alpha=1.0 / n, beta=lam, z=v)
             be.trmv(P, "LAi", u, out=out1)
-            u = be.trmv(P, "LTi", cc2[1], alpha=1.0 / n, beta=lam, z=v2)
+            u = be.trmv(P, "LTi", cc2[1, :M], alpha=1.0 / n, beta=lam, z=v2)
             be.trmv(P, "LAi", u, out=out2)
 
     b0 = ar(b0)                                        # K' (y / n), summed over shards
