@@ -222,6 +222,15 @@ int64_t odx_knm_fwd_bwd2_q_workspace_bytes(int64_t n, int64_t M, int fmt);
 int odx_knm_fwd_bwd2_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
                        const double* v, const double* v2, double* out, double* out2, void* workspace,
                        int64_t workspace_bytes, odx_stream_t stream);
+/* out[q] = K' (K v[q]), q = 0 .. nv - 1, 3 <= nv <= 8, from ONE read of a compact-format block (what a lambda path's CG
+ * states share: odx.solver.falkon_fit_path).  V / out: nv f64 rows, ldv / ldo doubles apart (even, >= M), 16-byte aligned.
+ * The vectors sit in LDS as f64, so the widths that exist are nv <= 8 up to M = 2524 and nv <= 4 up to M = 5084; the
+ * workspace twin returns a negative value for any other (M, fmt, nv) and the call ODX_ERR_UNSUPPORTED.  Slab per workgroup
+ * and vector, fixed-order reduction: bitwise reproducible, no atomics. */
+int64_t odx_knm_fwd_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv);
+int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
+                       const double* V, int64_t ldv, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
+                       odx_stream_t stream);
 /* out[r * ldo] = (float) sum_j K[r, j] alpha[j], r < n, over a stored block in any of the three formats (scores from the
  * block a fit streamed: one read of it instead of a second Gaussian contraction).  Accumulated in f64 in a fixed order
  * (bitwise reproducible); no workspace.  M <= 20476; ldk (and ldlo for ODX_KNM_U24) a multiple of 4, >= roundup(M, 4);
@@ -283,6 +292,14 @@ int odx_falkon_precond_f64(const float* Z, int64_t ldz, int64_t M, int D, double
                            double lam, double eps, double* LTi, double* LTit, double* LAi,
                            double* LAit, int64_t ld, int32_t* info,
                            void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* The preconditioners of a lambda path: L <= 32 values lams[l] (HOST array) for the same centres.  L_T, its inverses and
+ * T T'/M are made once; member l gets its own L_A(lams[l]) and inverses by the launches of odx_falkon_precond_f64, so its
+ * factors equal that call's bit for bit.  LTi / LTit as above (shared by all members); LA: L blocks of two M x ld matrices,
+ * member l's LAi at LA + 2 l M ld and its LAit M ld behind it.  info: L words. */
+int64_t odx_falkon_precond_path_workspace_bytes(int64_t M, int D, int L);
+int odx_falkon_precond_path_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
+                                double eps, double* LTi, double* LTit, double* LA, int64_t ld, int32_t* info,
+                                void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 /* The same preconditioner for B <= 32 independent classes at once (the reference trains its classes one after the
  * other, OnlineRegionClassifier_incore.py:96-155 — each `classifier.train` call above builds one; the classes are
  * independent, so here every launch of the factorisation chain advances all B).  Z[b] / ldz[b] / M[b]: HOST arrays of

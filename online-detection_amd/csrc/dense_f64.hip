@@ -1023,8 +1023,10 @@ extern "C" int64_t odx_falkon_precond_workspace_bytes(int64_t M, int D) {
   return dbl * (int64_t)sizeof(double);
 }
 
-static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, double lam,
-                                   double eps, double* LTi, double* LTit, double* LAi, double* LAit, int64_t ld,
+// (one chain for a whole lambda path: everything up to T T'/M once, then per member l its own  + lams[l] I -> L_A -> inverses;
+// L = 1 is the plain preconditioner, factored in place)
+static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
+                                   double eps, double* LTi, double* LTit, double* const* LAi, double* const* LAit, int64_t ld,
                                    int32_t* info, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 // (Left alive, the idle helper streams of a class-batched chain slow every later small launch of the process: the caller
@@ -1032,19 +1034,45 @@ static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D
 extern "C" int odx_falkon_precond_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, double lam,
                                       double eps, double* LTi, double* LTit, double* LAi, double* LAit, int64_t ld,
                                       int32_t* info, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
-  const int rc = falkon_precond_f64_impl(Z, ldz, M, D, sigma, lam, eps, LTi, LTit, LAi, LAit, ld, info, workspace, workspace_bytes, stream);
+  ODX_REQUIRE(LAi && LAit, "odx_falkon_precond_f64: null pointer");
+  const int rc = falkon_precond_f64_impl(Z, ldz, M, D, sigma, &lam, 1, eps, LTi, LTit, &LAi, &LAit, ld, info, workspace, workspace_bytes, stream);
   return rc;
 }
 
-static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, double lam,
-                                   double eps, double* LTi, double* LTit, double* LAi, double* LAit, int64_t ld,
+// The preconditioners of a lambda path: L_T, its inverses and T T'/M do not depend on lambda, so they are made once; member l
+// gets its own copy of T T'/M, + lams[l] I, Cholesky and inverses — by the very launches odx_falkon_precond_f64 issues, so
+// its factors are that call's bit for bit.  workspace: the single call's, then one more M x ld matrix (the member being factored).
+extern "C" int64_t odx_falkon_precond_path_workspace_bytes(int64_t M, int D, int L) {
+  if (M <= 0 || D <= 0 || L <= 0) return 0;
+  return round_up(odx_falkon_precond_workspace_bytes(M, D), 16) + (L > 1 ? M * precond_ld(M) * (int64_t)sizeof(double) : 0);
+}
+
+extern "C" int odx_falkon_precond_path_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
+                                           double eps, double* LTi, double* LTit, double* LA, int64_t ld, int32_t* info,
+                                           void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(lams && LA && L >= 1 && L <= ODX_MAX_ZBATCH, "odx_falkon_precond_path_f64: 1 <= L <= %d lambdas, non-null lams / LA",
+              ODX_MAX_ZBATCH);
+  ODX_REQUIRE(M > 0 && ld >= M, "odx_falkon_precond_path_f64: bad sizes");
+  double* lai[ODX_MAX_ZBATCH];
+  double* lait[ODX_MAX_ZBATCH];
+  for (int l = 0; l < L; ++l) {
+    lai[l] = LA + (int64_t)(2 * l) * M * ld;
+    lait[l] = lai[l] + M * ld;
+  }
+  return falkon_precond_f64_impl(Z, ldz, M, D, sigma, lams, L, eps, LTi, LTit, lai, lait, ld, info, workspace, workspace_bytes, stream);
+}
+
+static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
+                                   double eps, double* LTi, double* LTit, double* const* LAi, double* const* LAit, int64_t ld,
                                    int32_t* info, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
   ODX_REQUIRE(M > 0 && D > 0 && sigma > 0, "odx_falkon_precond_f64: bad sizes");
-  ODX_REQUIRE(Z && LTi && LTit && LAi && LAit && info && workspace, "odx_falkon_precond_f64: null pointer");
-  ODX_REQUIRE(ld % 2 == 0 && ld >= M && aligned16(LTi) && aligned16(LTit) && aligned16(LAi) && aligned16(LAit),
-              "odx_falkon_precond_f64: outputs must be 16-byte aligned with even ld >= M");
+  ODX_REQUIRE(Z && LTi && LTit && info && workspace, "odx_falkon_precond_f64: null pointer");
+  ODX_REQUIRE(ld % 2 == 0 && ld >= M && aligned16(LTi) && aligned16(LTit), "odx_falkon_precond_f64: outputs must be 16-byte aligned with even ld >= M");
+  for (int l = 0; l < L; ++l)
+    ODX_REQUIRE(LAi[l] && LAit[l] && aligned16(LAi[l]) && aligned16(LAit[l]),
+                "odx_falkon_precond_f64: outputs must be 16-byte aligned with even ld >= M");
   ODX_REQUIRE(aligned16(workspace), "odx_falkon_precond_f64: workspace must be 16-byte aligned");
-  if (workspace_bytes < odx_falkon_precond_workspace_bytes(M, D)) {
+  if (workspace_bytes < odx_falkon_precond_path_workspace_bytes(M, D, L)) {
     set_error("odx_falkon_precond_f64: workspace too small");
     return ODX_ERR_WORKSPACE;
   }
@@ -1066,14 +1094,18 @@ static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D
   const int64_t ldpt = h2_f64_packed_ld(M);
   uint32_t* Tk = reinterpret_cast<uint32_t*>(DinvA + dsz);             // packed T (later: merge-level packs), then the two packed panels
   uint32_t* Pk = Tk + precond_pack_units(M);
+  // a path keeps T T'/M in W2 and factors each member in a matrix of its own behind the single call's workspace
+  double* WA = L > 1 ? static_cast<double*>(workspace) + round_up(odx_falkon_precond_workspace_bytes(M, D), 16) / (int64_t)sizeof(double) : W2;
 
-  ODX_CHECK_HIP(hipMemsetAsync(info, 0, sizeof(int32_t), s));
+  ODX_CHECK_HIP(hipMemsetAsync(info, 0, (size_t)L * sizeof(int32_t), s));
   ODX_CHECK_HIP(hipMemsetAsync(Zd, 0, (size_t)(M * ldzd) * sizeof(double), s));
   ODX_PROPAGATE(odx_convert_f32_f64(Z, ldz, Zd, ldzd, M, D, stream));
   // W0 = K_MM + eps*M*I (lower), then L_T in place
   ODX_CHECK_HIP(hipMemsetAsync(W0, 0, (size_t)(M * wld) * sizeof(double), s));
   ODX_PROPAGATE(gauss_kmm_f64(Zd, ldzd, M, D, sigma, eps * (double)M, W0, wld, zsq, s));
   ODX_PROPAGATE(potrf_f64(W0, wld, M, DinvT, info, s));
+  for (int l = 1; l < L; ++l)      // a failed pivot of L_T is every member's
+    ODX_CHECK_HIP(hipMemcpyAsync(info + l, info, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   // fork: inverses of L_T on the side stream (scratch W3)
   ODX_CHECK_HIP(hipEventRecord(side->fork, s));
   ODX_CHECK_HIP(hipStreamWaitEvent(s2, side->fork, 0));
@@ -1085,34 +1117,38 @@ static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D
   ODX_CHECK_HIP(hipMemsetAsync(W1, 0, (size_t)(M * wld) * sizeof(double), s));
   ODX_PROPAGATE(transpose_f64(W0, wld, W1, wld, M, M, s));
   ODX_CHECK_HIP(hipMemsetAsync(W2, 0, (size_t)(M * wld) * sizeof(double), s));
+  // |T_ij| <= sqrt(max diagonal of T'T) = sqrt(1 + eps M);  |L_A ij| <= sqrt(max diagonal of T T' / M + lam) <= sqrt(1 + eps + lam)
+  // (M < 65536 everywhere in this file: one bound for every call, so that the class-batched chain packs with the very
+  // scales of the single-class one and stays bit-identical to it)
   if (split) {
-    // |T_ij| <= sqrt(max diagonal of T'T) = sqrt(1 + eps M);  |L_A ij| <= sqrt(max diagonal of T T' / M + lam) <= sqrt(1 + eps + lam)
-    // (M < 65536 everywhere in this file: one bound for every call, so that the class-batched chain packs with the very
-    // scales of the single-class one and stays bit-identical to it)
-    const float st = split_scale_for(sqrt(1.0 + eps * 65536.0)), sa = split_scale_for(sqrt(1.0 + eps + lam));
+    const float st = split_scale_for(sqrt(1.0 + eps * 65536.0));
     const double a1 = 1.0 / (double)M;
     ODX_PROPAGATE(split_f64(W1, wld, 0, M, M, st, Tk, ldpt, 0, 1, s));
     ODX_PROPAGATE(gemm_h2_f64(Tk, ldpt, 0, st, Tk, ldpt, 0, st, W2, wld, 0, M, M, M, &a1, 0.0,
                               ODX_GEMM_LOWER_ONLY | ODX_GEMM_A_UPPER | ODX_GEMM_B_UPPER, 1, s));
-    ODX_PROPAGATE(add_diag_f64(W2, wld, M, lam, s));
-    ODX_PROPAGATE(potrf_f64(W2, wld, M, DinvA, info, s, ZBatch(), Pk, M * POTRF_NBO, 0, sa));
   } else {
     GemmParams<double> g;
     g.A = W1; g.lda = wld; g.B = W1; g.ldb = wld; g.C = W2; g.ldc = wld;
     g.m = M; g.n = M; g.k = M; g.alpha = 1.0 / (double)M; g.beta = 0.0;
     g.flags = ODX_GEMM_LOWER_ONLY | ODX_GEMM_A_UPPER | ODX_GEMM_B_UPPER;
     ODX_PROPAGATE(launch_gemm_f64(g, s));
-    ODX_PROPAGATE(add_diag_f64(W2, wld, M, lam, s));
-    ODX_PROPAGATE(potrf_f64(W2, wld, M, DinvA, info, s));
   }
-  // join, then the inverses of L_A (scratch W1: T is no longer needed)
-  ODX_CHECK_HIP(hipStreamWaitEvent(s, side->join, 0));
-  ODX_PROPAGATE(fill_f64(LAi, ld, M, M, 0.0, s));
-  ODX_PROPAGATE(fill_f64(LAit, ld, M, M, 0.0, s));
-  if (split && eps + lam > 0.0)
-    return trtri_from_diag_f64(W2, wld, M, DinvA, LAi, LAit, ld, W1, s, ZBatch(), Tk, precond_pack_units(M), 0, sqrt(1.0 + eps + lam),
-                               1.0 / sqrt(eps + lam));
-  ODX_PROPAGATE(trtri_from_diag_f64(W2, wld, M, DinvA, LAi, LAit, ld, W1, s));
+  for (int l = 0; l < L; ++l) {
+    const double lam = lams[l];
+    if (WA != W2) ODX_CHECK_HIP(hipMemcpyAsync(WA, W2, (size_t)(M * wld) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    ODX_PROPAGATE(add_diag_f64(WA, wld, M, lam, s));
+    if (split) ODX_PROPAGATE(potrf_f64(WA, wld, M, DinvA, info + l, s, ZBatch(), Pk, M * POTRF_NBO, 0, split_scale_for(sqrt(1.0 + eps + lam))));
+    else ODX_PROPAGATE(potrf_f64(WA, wld, M, DinvA, info + l, s));
+    // join (once), then the inverses of L_A (scratch W1: T is no longer needed)
+    if (l == 0) ODX_CHECK_HIP(hipStreamWaitEvent(s, side->join, 0));
+    ODX_PROPAGATE(fill_f64(LAi[l], ld, M, M, 0.0, s));
+    ODX_PROPAGATE(fill_f64(LAit[l], ld, M, M, 0.0, s));
+    if (split && eps + lam > 0.0)
+      ODX_PROPAGATE(trtri_from_diag_f64(WA, wld, M, DinvA, LAi[l], LAit[l], ld, W1, s, ZBatch(), Tk, precond_pack_units(M), 0,
+                                        sqrt(1.0 + eps + lam), 1.0 / sqrt(eps + lam)));
+    else
+      ODX_PROPAGATE(trtri_from_diag_f64(WA, wld, M, DinvA, LAi[l], LAit[l], ld, W1, s));
+  }
   return ODX_OK;
 }
 

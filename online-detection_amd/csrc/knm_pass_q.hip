@@ -21,36 +21,9 @@
 #include <stdlib.h>
 
 #include "odx_internal.h"
+#include "knm_q.h"
 
 namespace odx {
-
-typedef unsigned int u32x4q __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2q __attribute__((ext_vector_type(2)));
-typedef double f64x2q __attribute__((ext_vector_type(2)));
-
-enum { QF_U24 = 1, QF_BF16 = 2 };      // = ODX_KNM_U24 / ODX_KNM_BF16
-
-// A thread's chunk: CW = 4 consecutive columns of a row — two dwords of the u16 plane, one of the u8 plane (the f32 kernel's
-// columns per thread, so the same (NT, CH) cover a row; 8-column chunks with 16-byte loads measured no faster).
-constexpr int QCW = 4;
-template <int FMT, int CW>
-struct QChunk {
-  unsigned hi[CW / 2];
-  unsigned lo[CW / 4];
-};
-
-// entry e (0 .. CW - 1) of a chunk as a double: the integer q for QF_U24 (value = q 2^-24), the value itself for QF_BF16
-template <int FMT, int CW>
-__device__ __forceinline__ double q_entry(const QChunk<FMT, CW>& k, int e) {
-  const unsigned h = k.hi[e >> 1];
-  if (FMT == QF_U24) {
-    // v_perm_b32: selector bytes 0..3 pick bytes of the second source (the low-byte dword), 4..7 bytes of the first (the
-    // u16 pair), 0x0c a zero byte: result = [low byte (e & 3) | u16 << 8]
-    const unsigned sel = ((e & 1) ? 0x0c070600u : 0x0c050400u) | (unsigned)(e & 3);
-    return (double)__builtin_amdgcn_perm(h, k.lo[e >> 2], sel);
-  }
-  return (double)__uint_as_float((e & 1) ? (h & 0xffff0000u) : (h << 16));
-}
 
 template <int NT, int CH, int R, int NV, int FMT, int WPE>
 __device__ __forceinline__ void knm_passq_body(const unsigned short* __restrict__ Khi, int64_t ldk,
@@ -489,7 +462,7 @@ static bool pick_qcfg(int64_t M, int nv, int fmt, QCfg* cfg) {
 // of the CU partition the passes' stream is confined to, odx_stream_create_cu_mask)
 static int g_pass_cus = 0;
 
-static int pass_cus() {
+int pass_cus() {
   if (g_pass_cus > 0) return g_pass_cus;
   const int cus = odx_device_cus();
   return cus > 0 ? cus : 256;
@@ -547,7 +520,7 @@ static int dispatch_passq(const QCfg& cfg, int grid, size_t lds, hipStream_t s, 
 #undef ODX_Q
 }
 
-static int check_q_block(const char* who, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t M) {
+int check_q_block(const char* who, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t M) {
   ODX_REQUIRE(fmt == ODX_KNM_U24 || fmt == ODX_KNM_BF16, "%s: storage format must be ODX_KNM_U24 or ODX_KNM_BF16 (got %d)", who, fmt);
   // (row sub-blocks of a stored shard are valid arguments: the planes need the alignment of one chunk load only)
   ODX_REQUIRE(K && ldk % 8 == 0 && ldk >= round_up(M, 8) && (reinterpret_cast<uintptr_t>(K) & 7u) == 0,

@@ -85,6 +85,11 @@ int knm_passq_batched(int B, const void* const* Khi, const int64_t* ldk, const v
                       const int64_t* n, const int64_t* M, const double* v, int64_t vstride, double* out, int64_t ostride,
                       void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+// knm_pass_q.hip, shared with knm_pass_nv.hip: the compute units the persistent pass grids are sized for (the device's, or
+// odx_set_pass_cus), and the argument checks of a compact-format block
+int pass_cus();
+int check_q_block(const char* who, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t M);
+
 // knm_pass.hip: the CG pass for a batch of classes (one launch; per class the arithmetic of odx_knm_fwd_bwd)
 bool knm_pass_batch_cfg(int B, const int64_t* M, int* nt, int* ch, int* r);
 int64_t knm_pass_batched_workspace_bytes(int B, const int64_t* n, const int64_t* M);

@@ -20,6 +20,7 @@ import os
 import torch
 
 from . import hip
+from .knm_path import PathOps
 
 
 def _p(t):
@@ -110,7 +111,7 @@ class KnmStream:
 _KNM_CODE = {"f32": hip.KNM_F32, "u24": hip.KNM_U24, "bf16": hip.KNM_BF16}
 
 
-class HipBackend:
+class HipBackend(PathOps):
     name = "hip-gfx950"
 
     def __init__(self, device=None):

@@ -20,7 +20,7 @@ import torch
 
 from . import backend as _backend
 from . import options as _options
-from .solver import SolverOptions, falkon_fit
+from .solver import SolverOptions, falkon_fit, falkon_fit_path
 
 
 class FalkonOptions:
@@ -129,6 +129,41 @@ class _FalkonBase:
         else:
             self._centres(Zf)
         return self
+
+    def fit_path(self, X, Y, penalties):
+        """One fitted estimator of this class per penalty, from one K_nM block (solver.falkon_fit_path): the centres are
+        selected once and shared (`ny_points_`), each estimator has its own `penalty` and `alpha_`.  This estimator is the
+        template and stays as it is."""
+        import copy
+        be = _backend.get_backend()
+        F = be.features(X)
+        if isinstance(self.center_selection, str):
+            Zf = be.rows(F, torch.randperm(F.n)[: self.M])
+        else:
+            sel = self.center_selection.select(F.X, None)
+            Zf = be.features(sel[0] if isinstance(sel, tuple) else sel)
+        y = torch.as_tensor(Y).reshape(F.n, -1)
+        if y.shape[1] != 1:
+            raise ValueError("odx FALKON fits one right-hand side per model (the reference trains one "
+                             "binary classifier per fit); got Y with %d columns" % y.shape[1])
+        penalties = [float(p) for p in penalties]
+        alphas = falkon_fit_path(be, F, be.vec(y[:, 0]), Zf, self.kernel.sigma, penalties, int(self.maxiter),
+                                 self.options.solver_options())
+        if hasattr(be, "release_helper_streams"):
+            be.release_helper_streams()
+        ny = Zf.X.contiguous() if Zf.X.stride(0) != Zf.D else Zf.X
+        out = []
+        for l, pen in enumerate(penalties):
+            est = copy.copy(self)
+            est.__dict__.pop("_zf", None)
+            est.penalty, est.M = pen, Zf.n
+            est.alpha_, est.ny_points_ = alphas[l].clone().reshape(-1, 1), ny
+            if est._cpu_model:
+                est.alpha_, est.ny_points_ = est.alpha_.cpu(), est.ny_points_.cpu()
+            else:
+                est._centres(Zf)
+            out.append(est)
+        return out
 
     def _centres(self, Zf=None):
         """The centres as kernel operands (row norms, packed f16 split), kept with the model while `ny_points_` is the

@@ -1,0 +1,88 @@
+"""Backend operations of a lambda path (solver.falkon_fit_path): L fits that share one K_nM block.
+
+``PathOps`` is mixed into ``backend.HipBackend``.  It adds the pass over several vectors from one read of the block
+(``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, the existing one- and two-vector passes for the rest) and the
+preconditioners of a lambda path (``precond_path``: odx_falkon_precond_path_f64), both HIP through libodx.
+"""
+import ctypes
+
+import torch
+
+from . import hip
+
+_CODE = {"u24": hip.KNM_U24, "bf16": hip.KNM_BF16}
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+class PathOps:
+    def _ktkn_bytes(self, K, nv):
+        return self.lib.odx_knm_fwd_bwdn_q_workspace_bytes(max(K.n, 1), K.M, _CODE[K.fmt], nv)
+
+    def ktkn_width(self, K):
+        """The largest number of vectors ONE read of K serves: 8 or 4 where the NV-vector pass over a compact block has a
+        configuration (the vectors sit in LDS as f64: 8 up to M = 2524, 4 up to M = 5084), else 2 where the two-vector pass
+        exists, else 1.  f32 blocks (small, not HBM-bound) and streamed shards are served by ktk / ktk2 only."""
+        if K.fmt in _CODE:
+            for nv in (8, 4):
+                if self._ktkn_bytes(K, nv) >= 0:
+                    return nv
+        return 2 if self.can_ktk2(K) else 1
+
+    def ktkn(self, K, V, out=None):
+        """out[l] = K' (K V[l]) for the L >= 1 rows of V ((L, ld) f64), with as few reads of K as its width allows: groups of
+        ktkn_width(K) rows, a group of 3 .. 8 by odx_knm_fwd_bwdn_q, of 2 by ktk2 (two ktk where the block has no two-vector
+        pass), of 1 by ktk.  Columns [0, K.M) of V / out are used; rows must be 16-byte aligned for groups of 3 or more."""
+        L, M = V.shape[0], K.M
+        if out is None:
+            out = torch.zeros((L, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
+        for t in (V, out):
+            if t.dim() != 2 or t.shape[0] != L or t.shape[1] < M or t.dtype != torch.float64 or t.stride(1) != 1:
+                raise ValueError("ktkn: V and out must be (L, >= M) f64 matrices with contiguous rows")
+        width = self.ktkn_width(K)
+        for l in range(0, L, width):
+            g = min(width, L - l)
+            if g >= 3:
+                if V.stride(0) % 2 or out.stride(0) % 2 or V[l].data_ptr() % 16 or out[l].data_ptr() % 16:
+                    raise ValueError("ktkn: rows of V and out must be 16-byte aligned (even leading dimension)")
+                ws = self._workspace("ktk", self._ktkn_bytes(K, g))
+                hip.check(self.lib.odx_knm_fwd_bwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], K.n, M, g,
+                                                      _p(V[l]), V.stride(0), _p(out[l]), out.stride(0), _p(ws), ws.numel(),
+                                                      self._stream()), "odx_knm_fwd_bwdn_q")
+            elif g == 2 and self.can_ktk2(K):
+                self.ktk2(K, V[l, :M], V[l + 1, :M], out1=out[l, :M], out2=out[l + 1, :M])
+            else:
+                for j in range(l, l + g):
+                    self.ktk(K, v=V[j, :M], out=out[j, :M])
+        return out
+
+    def precond_path(self, Zf, sigma, lams, eps, out=None, ws_key="precond"):
+        """One Precond per value of `lams` for the same centres.  The members share LTi / LTit (they do not depend on
+        lambda) and own their LAi / LAit; member l equals precond(Zf, sigma, lams[l], eps) bit for bit.  `out`: optional
+        (2 + 2 L, M, ld) f64 tensor.  A member's info is its word of one (L,) tensor."""
+        from .backend import Precond
+        lams = [float(x) for x in lams]
+        L, M, D = len(lams), Zf.n, Zf.D
+        if not 1 <= L <= self.MAX_CLASS_BATCH:
+            raise ValueError("precond_path: 1..%d lambdas per call, got %d" % (self.MAX_CLASS_BATCH, L))
+        ld = (M + 1) // 2 * 2
+        shape = (2 + 2 * L, M, ld)
+        mats = out if out is not None else torch.empty(shape, dtype=torch.float64, device=self.device)
+        if mats.dtype != torch.float64 or tuple(mats.shape) != shape or not mats.is_contiguous():
+            raise ValueError("precond_path: out must be a contiguous %r f64 tensor" % (shape,))
+        info = torch.zeros(L, dtype=torch.int32, device=self.device)
+        ws = self._workspace(ws_key, self.lib.odx_falkon_precond_path_workspace_bytes(M, D, L))
+        hip.check(self.lib.odx_falkon_precond_path_f64(_p(Zf.X), Zf.ld, M, D, float(sigma), (ctypes.c_double * L)(*lams), L, float(eps),
+                                                       _p(mats[0]), _p(mats[1]), _p(mats[2]), ld, _p(info), _p(ws), ws.numel(),
+                                                       self._stream()), "odx_falkon_precond_path_f64")
+        members = []
+        for l in range(L):
+            P = Precond()
+            P.M, P.ld = M, ld
+            P.LTi, P.LTit, P.LAi, P.LAit = mats[0], mats[1], mats[2 + 2 * l], mats[3 + 2 * l]
+            P.block_rows = None          # not one (4, M, ld) block: the class-batched library loop does not take it
+            P.info = info[l:l + 1]
+            members.append(P)
+        return members

@@ -244,6 +244,94 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     return alpha
 
 
+def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=None, allreduce=None, phase=None, knm_out=None,
+                    knm_blocks=None):
+    """Fit one binary FALKON problem at every penalty of `lams` from ONE K_nM block.
+
+    Nothing before `+ lam I` depends on lambda: the block, its right-hand side, T, T^-1 and T T'/M are made once
+    (be.knm_rhs, be.precond_path), and the L conjugate-gradient states — one per lambda, each following falkon_fit's
+    schedule exactly, with its own device-side stop flag — share every read of the block: per iteration one be.ktkn over
+    the L directions (phase "ktkn"), and one more over the L iterates for the periodic full residual (its plain form
+    R = B - W x; the fold of falkon_fit needs two vectors per member).  No host synchronisation inside the loop.
+
+    One shard, or replicated row shards through `allreduce` (in-place sum of an f64 device tensor: the (M,) right-hand
+    side once, the (L, Mp) matrix of partial products once per pass).  A backend without ktkn / precond_path is served
+    by looping ktk / precond.  Other arguments as falkon_fit.  Returns the alphas, (L, M) f64."""
+    import math
+    opt = opt or SolverOptions()
+    lams = [float(x) for x in lams]
+    if not lams or any(not (math.isfinite(x) and x > 0.0) for x in lams):
+        raise ValueError("falkon_fit_path: lams must be a non-empty sequence of finite positive penalties, got %r" % (lams,))
+    L = len(lams)
+    n = float(F.n if n_total is None else n_total)
+    M = Zf.n
+    Mp = (M + 1) // 2 * 2                                # rows of the shared matrices stay 16-byte aligned
+    ar = allreduce if allreduce is not None else (lambda v: v)
+    ph = phase if phase is not None else (lambda name: _NoPhase())
+
+    with ph("precond"):
+        if hasattr(be, "precond_path"):
+            Ps = be.precond_path(Zf, sigma, lams, opt.pc_epsilon)
+        else:
+            Ps = [be.precond(Zf, sigma, lam, opt.pc_epsilon) for lam in lams]
+    with ph("knm"):
+        K, b0 = be.knm_rhs(F, Zf, sigma, y * (1.0 / n), out=knm_out)
+    if knm_blocks is not None:
+        knm_blocks.append(K)
+    b0 = ar(b0)                                          # K' (y / n), summed over shards
+
+    TT = be.zeros(L * Mp).view(L, Mp)                    # row l: T^-1 A_l^-1 s_l, the vector member l sends through K'K
+    CC = be.zeros(L * Mp).view(L, Mp)                    # row l: K'K of it
+    vs = [be.zeros(M) for _ in range(L)]
+
+    def mmv_all(S, out):
+        """out[l] = W_l S[l] for every member, W_l = A_l^-T [ T^-T K'K (T^-1 A_l^-1 .) / n + lam_l A_l^-1 . ], one pass over K."""
+        for l, P in enumerate(Ps):
+            be.trmv(P, "LAit", S[l], out=vs[l])
+            be.trmv(P, "LTit", vs[l], out=TT[l, :M])
+        with ph("ktkn"):
+            if hasattr(be, "ktkn"):
+                be.ktkn(K, TT, out=CC)
+            else:
+                for l in range(L):
+                    be.ktk(K, v=TT[l, :M], out=CC[l, :M])
+        r = ar(CC)
+        if r is not CC:
+            CC.copy_(r)
+        for l, P in enumerate(Ps):
+            u = be.trmv(P, "LTi", CC[l, :M], alpha=1.0 / n, beta=lams[l], z=vs[l])
+            be.trmv(P, "LAi", u, out=out[l])
+
+    X, R, Pv, AP = ([be.zeros(M) for _ in range(L)] for _ in range(4))
+    states = [be.zeros(4) for _ in range(L)]
+    Bs = []
+    for l, P in enumerate(Ps):
+        Bs.append(be.trmv(P, "LAi", be.trmv(P, "LTi", b0)))      # A_l^-T T^-T b0
+        be.cg_init(Bs[l], X[l], R[l], Pv[l], states[l])
+    tol = opt.cg_tolerance ** 2
+    for it in range(maxiter):
+        full = (it + 1) % opt.cg_full_gradient_every == 0
+        mmv_all(Pv, AP)
+        for l in range(L):
+            be.cg_step(X[l], R[l], Pv[l], AP[l], states[l], opt.cg_epsilon, full)
+        if it == maxiter - 1:
+            break    # the residual / direction update of the last step cannot change the returned X
+        if full:
+            mmv_all(X, AP)
+            for l in range(L):
+                R[l].copy_(Bs[l])
+                be.axpby(-1.0, AP[l], 1.0, R[l])         # R = B - W x
+        for l in range(L):
+            be.cg_finish(R[l], Pv[l], states[l], opt.cg_epsilon, tol)
+    alphas = be.zeros(L * M).view(L, M)
+    for l, P in enumerate(Ps):
+        alphas[l].copy_(be.trmv(P, "LTit", be.trmv(P, "LAit", X[l])))    # T^-1 A_l^-1 beta_l
+    if opt.check_pivots:
+        for P in Ps:
+            _check_pivots(be, P)
+    return alphas
+
+
 def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_total=None, shard=None, knm_outs=None,
                         phase=None, precond=None, precond_ready=None, owners=None, knm_blocks=None):
     """Fit up to `world` binary problems at once over row shards, one owner rank per problem.
