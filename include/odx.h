@@ -252,6 +252,22 @@ int odx_gauss_ktk_stream_h2(const void* PX, int64_t ldpx, const float* metax, co
                             const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
                             double sigma, const double* v, const double* v2, const double* w, double* out, double* out2,
                             void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* out[q] = K' (K V[q]), q = 0 .. nv - 1, over a shard that is never stored, with K built ONCE per call (what a lambda path's CG
+ * iteration needs on a streamed shard: odx_gauss_ktk_stream_h2 would rebuild K for every pair of vectors).  1 <= nv <=
+ * ODX_STREAM_MAX_VECTORS; rows of V / out 16-byte aligned with even ldv, ldo >= M; the other arguments as odx_gauss_ktk_stream_h2.
+ * Per chunk of odx_gauss_ktk_stream_h2n_rows(M, D) rows: one odx_gauss_knm_h2_store into the ring (ODX_KNM_U24, the entries of the
+ * stored block), then the vectors in groups of the widest pass that exists at this M, each reading the resident chunk and
+ * reusing one slab workspace (odx_knm_fwd_bwdn_q: 8 up to M = 2524, 4 up to M = 5084, and a remainder of 3 or more;
+ * odx_knm_fwd_bwd2_q for pairs where it exists; odx_knm_fwd_bwd_q otherwise), then ONE launch adds the chunk's nv vectors into
+ * out.  f64 sums in a fixed order, no atomics: bitwise reproducible.  M <= 20440 (ODX_ERR_UNSUPPORTED above, and a negative
+ * workspace size for any unsupported (M, nv)); the workspace does not grow with n or nv and stays below 256 MiB. */
+#define ODX_STREAM_MAX_VECTORS 16
+int64_t odx_gauss_ktk_stream_h2n_rows(int64_t M, int D);
+int64_t odx_gauss_ktk_stream_h2n_workspace_bytes(int64_t n, int64_t M, int D, int nv);
+int odx_gauss_ktk_stream_h2n(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                             const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                             double sigma, int nv, const double* V, int64_t ldv, double* out, int64_t ldo,
+                             void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 /* ---------------------------------------------------------------- A3 / A5 with the fp8 contraction (BASELINE config 5)
  * "fp8 (OCP e4m3) inputs to the X Z' MFMA, f32 accumulate, stress / throughput only" (cfg 5; the reference's own

@@ -133,7 +133,8 @@ class _FalkonBase:
     def fit_path(self, X, Y, penalties):
         """One fitted estimator of this class per penalty, from one K_nM block (solver.falkon_fit_path): the centres are
         selected once and shared (`ny_points_`), each estimator has its own `penalty` and `alpha_`.  This estimator is the
-        template and stays as it is."""
+        template and stays as it is.  Under knm_storage "stream" (no block: K is recomputed by the passes) up to 8 penalties
+        cost one recompute of K per CG iteration, 9 .. 16 one per iteration plus one per full residual."""
         import copy
         be = _backend.get_backend()
         F = be.features(X)

@@ -14,6 +14,7 @@ _LIB_PATH = os.environ.get("ODX_LIB_PATH") or os.path.join(os.path.dirname(os.pa
 
 ODX_OK = 0
 KNM_F32, KNM_U24, KNM_BF16 = 0, 1, 2
+STREAM_MAX_VECTORS = 16      # ODX_STREAM_MAX_VECTORS: vectors one odx_gauss_ktk_stream_h2n call serves from one build of K
 GEMM_LOWER_ONLY, GEMM_A_UPPER, GEMM_B_UPPER, GEMM_A_LOWER, GEMM_B_LOWER, GEMM_STORE_T = 1, 2, 4, 8, 16, 32
 
 
@@ -88,6 +89,10 @@ SIGNATURES = {
     "odx_gauss_ktk_stream_h2_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "odx_gauss_ktk_stream_h2": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _i64, _vp]),
+    "odx_gauss_ktk_stream_h2n_rows": (_i64, [_i64, _i32]),
+    "odx_gauss_ktk_stream_h2n_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "odx_gauss_ktk_stream_h2n": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _i32, _vp, _i64, _vp, _i64,
+                                        _vp, _i64, _vp]),
     "odx_split_f8": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
     "odx_gauss_knm_f8_store": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _i32, _vp, _i64, _vp, _i64,
                                       _vp, _vp, _vp, _i64, _vp]),

@@ -1,8 +1,8 @@
 """Backend operations of a lambda path (solver.falkon_fit_path): L fits that share one K_nM block.
 
 ``PathOps`` is mixed into ``backend.HipBackend``.  It adds the pass over several vectors from one read of the block
-(``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, the existing one- and two-vector passes for the rest) and the
-preconditioners of a lambda path (``precond_path``: odx_falkon_precond_path_f64), both HIP through libodx.
+(``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, the existing one- and two-vector passes for the rest; on a
+streamed shard odx_gauss_ktk_stream_h2n, up to 16 vectors from one BUILD of K) and the preconditioners of a lambda path (``precond_path``: odx_falkon_precond_path_f64), both HIP through libodx.
 """
 import ctypes
 
@@ -18,6 +18,9 @@ def _p(t):
 
 
 class PathOps:
+    """ktkn / ktkn_width / ktkn_span / precond_path of HipBackend.  On a streamed shard (KnmStream) ktkn makes ONE build of K
+    per group of ktkn_span = 16 vectors; ktkn_width keeps meaning vectors per READ of the block or ring (2 there)."""
+
     def _ktkn_bytes(self, K, nv):
         return self.lib.odx_knm_fwd_bwdn_q_workspace_bytes(max(K.n, 1), K.M, _CODE[K.fmt], nv)
 
@@ -31,16 +34,47 @@ class PathOps:
                     return nv
         return 2 if self.can_ktk2(K) else 1
 
+    def ktkn_span(self, K):
+        """The number of vectors ONE build-or-read of K serves in ktkn.  Stored blocks: ktkn_width(K), a read of the block.
+        Streamed shards: 16 (odx_gauss_ktk_stream_h2n builds each chunk of rows once and reads it back, while it is
+        resident in the Infinity Cache, once per group of vectors): a path of 8 can fold its full residual into the same build."""
+        return hip.STREAM_MAX_VECTORS if K.fmt == "stream" else self.ktkn_width(K)
+
+    def _ktkn_stream(self, K, V, out, l, g):
+        """Rows [l, l + g) of V through one build of the streamed shard (odx_gauss_ktk_stream_h2n).  The ring: the caller's
+        buffer when it is large enough for this entry (a buffer sized for ktk / ktk2 may not be), else the backend's."""
+        F, Zf = K.F, K.Zf
+        nbytes = int(self.lib.odx_gauss_ktk_stream_h2n_workspace_bytes(max(K.n, 1), K.M, F.D, g))
+        if nbytes < 0:
+            raise hip.OdxError("odx_gauss_ktk_stream_h2n: M = %d is outside the supported range (M <= 20440)" % K.M)
+        ws = K.ring if K.ring is not None and K.ring.numel() >= nbytes else self._workspace("ktkn_stream", nbytes)
+        hip.check(self.lib.odx_gauss_ktk_stream_h2n(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), K.n, _p(Zf.P), Zf.P.stride(0),
+                                                    _p(Zf.meta), _p(Zf.sq), K.M, F.D, K.sigma, g, _p(V[l]), V.stride(0), _p(out[l]),
+                                                    out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_ktk_stream_h2n")
+
     def ktkn(self, K, V, out=None):
         """out[l] = K' (K V[l]) for the L >= 1 rows of V ((L, ld) f64), with as few reads of K as its width allows: groups of
         ktkn_width(K) rows, a group of 3 .. 8 by odx_knm_fwd_bwdn_q, of 2 by ktk2 (two ktk where the block has no two-vector
-        pass), of 1 by ktk.  Columns [0, K.M) of V / out are used; rows must be 16-byte aligned for groups of 3 or more."""
+        pass), of 1 by ktk.  A streamed shard: groups of ktkn_span(K) = 16 rows, each from ONE build of K
+        (odx_gauss_ktk_stream_h2n; a single row goes through ktk).  Columns [0, K.M) of V / out are used; rows must be 16-byte
+        aligned for groups of 3 or more (on a streamed shard: of 2 or more)."""
         L, M = V.shape[0], K.M
         if out is None:
             out = torch.zeros((L, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
         for t in (V, out):
             if t.dim() != 2 or t.shape[0] != L or t.shape[1] < M or t.dtype != torch.float64 or t.stride(1) != 1:
                 raise ValueError("ktkn: V and out must be (L, >= M) f64 matrices with contiguous rows")
+        if K.fmt == "stream":
+            span = self.ktkn_span(K)
+            for l in range(0, L, span):
+                g = min(span, L - l)
+                if g == 1:
+                    self.ktk(K, v=V[l, :M], out=out[l, :M])
+                    continue
+                if V.stride(0) % 2 or out.stride(0) % 2 or V[l].data_ptr() % 16 or out[l].data_ptr() % 16:
+                    raise ValueError("ktkn: rows of V and out must be 16-byte aligned (even leading dimension)")
+                self._ktkn_stream(K, V, out, l, g)
+            return out
         width = self.ktkn_width(K)
         for l in range(0, L, width):
             g = min(width, L - l)

@@ -254,8 +254,13 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
     the L directions (phase "ktkn"), and one more over the L iterates for the periodic full residual (its plain form
     R = B - W x; the fold of falkon_fit needs two vectors per member).  No host synchronisation inside the loop.
 
+    A streamed shard (K.fmt "stream") recomputes K inside every ktkn, so there a second ktkn is a second build of K: when
+    the backend's ktkn_span(K) (vectors one build serves) holds 2 L, the full-residual iteration sends [directions;
+    iterates] through ONE ktkn and forms R_l = B_l - (W x_old + a W p) with be.cg_residual, as falkon_fit folds — one
+    build of K per CG iteration whatever L <= span / 2.  Stored blocks, and paths with 2 L > span, keep the plain form.
+
     One shard, or replicated row shards through `allreduce` (in-place sum of an f64 device tensor: the (M,) right-hand
-    side once, the (L, Mp) matrix of partial products once per pass).  A backend without ktkn / precond_path is served
+    side once, the (L, Mp) matrix of partial products once per pass; (2 L, Mp) at a folded iteration).  A backend without ktkn / precond_path is served
     by looping ktk / precond.  Other arguments as falkon_fit.  Returns the alphas, (L, M) f64."""
     import math
     opt = opt or SolverOptions()
@@ -280,27 +285,38 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
         knm_blocks.append(K)
     b0 = ar(b0)                                          # K' (y / n), summed over shards
 
-    TT = be.zeros(L * Mp).view(L, Mp)                    # row l: T^-1 A_l^-1 s_l, the vector member l sends through K'K
-    CC = be.zeros(L * Mp).view(L, Mp)                    # row l: K'K of it
-    vs = [be.zeros(M) for _ in range(L)]
+    # the fold of the periodic full residual (see the docstring): streamed shards whose one build serves 2 L vectors
+    can_fold = bool(getattr(K, "fmt", None) == "stream" and hasattr(be, "ktkn") and hasattr(be, "ktkn_span")
+                    and hasattr(be, "cg_residual") and 2 * L <= be.ktkn_span(K))
+    rows = 2 * L if can_fold else L
+    TT2 = be.zeros(rows * Mp).view(rows, Mp)             # row l: T^-1 A_l^-1 s_l, the vector member l sends through K'K
+    CC2 = be.zeros(rows * Mp).view(rows, Mp)             # row l: K'K of it   (rows L .. 2 L - 1: the iterates of a folded step)
+    TT, CC = TT2[:L], CC2[:L]
+    vs = [be.zeros(M) for _ in range(rows)]
 
-    def mmv_all(S, out):
-        """out[l] = W_l S[l] for every member, W_l = A_l^-T [ T^-T K'K (T^-1 A_l^-1 .) / n + lam_l A_l^-1 . ], one pass over K."""
-        for l, P in enumerate(Ps):
+    def mmv_rows(S, out, TTr, CCr):
+        """out[l] = W_m S[l] for the rows of S (member m = l mod L), W_m = A_m^-T [ T^-T K'K (T^-1 A_m^-1 .) / n + lam_m A_m^-1 . ],
+        from one ktkn over K."""
+        for l in range(len(S)):
+            P = Ps[l % L]
             be.trmv(P, "LAit", S[l], out=vs[l])
-            be.trmv(P, "LTit", vs[l], out=TT[l, :M])
+            be.trmv(P, "LTit", vs[l], out=TTr[l, :M])
         with ph("ktkn"):
             if hasattr(be, "ktkn"):
-                be.ktkn(K, TT, out=CC)
+                be.ktkn(K, TTr, out=CCr)
             else:
-                for l in range(L):
-                    be.ktk(K, v=TT[l, :M], out=CC[l, :M])
-        r = ar(CC)
-        if r is not CC:
-            CC.copy_(r)
-        for l, P in enumerate(Ps):
-            u = be.trmv(P, "LTi", CC[l, :M], alpha=1.0 / n, beta=lams[l], z=vs[l])
+                for l in range(len(S)):
+                    be.ktk(K, v=TTr[l, :M], out=CCr[l, :M])
+        r = ar(CCr)
+        if r is not CCr:
+            CCr.copy_(r)
+        for l in range(len(S)):
+            P = Ps[l % L]
+            u = be.trmv(P, "LTi", CCr[l, :M], alpha=1.0 / n, beta=lams[l % L], z=vs[l])
             be.trmv(P, "LAi", u, out=out[l])
+
+    def mmv_all(S, out):
+        mmv_rows(S, out, TT, CC)
 
     X, R, Pv, AP = ([be.zeros(M) for _ in range(L)] for _ in range(4))
     states = [be.zeros(4) for _ in range(L)]
@@ -309,14 +325,22 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
         Bs.append(be.trmv(P, "LAi", be.trmv(P, "LTi", b0)))      # A_l^-T T^-T b0
         be.cg_init(Bs[l], X[l], R[l], Pv[l], states[l])
     tol = opt.cg_tolerance ** 2
+    AX = [be.zeros(M) for _ in range(L)] if can_fold else None
     for it in range(maxiter):
         full = (it + 1) % opt.cg_full_gradient_every == 0
-        mmv_all(Pv, AP)
+        fold = can_fold and full and it != maxiter - 1
+        if fold:
+            mmv_rows(Pv + X, AP + AX, TT2, CC2)          # W p and W x_old of every member from one build of K
+        else:
+            mmv_all(Pv, AP)
         for l in range(L):
             be.cg_step(X[l], R[l], Pv[l], AP[l], states[l], opt.cg_epsilon, full)
         if it == maxiter - 1:
             break    # the residual / direction update of the last step cannot change the returned X
-        if full:
+        if fold:
+            for l in range(L):
+                be.cg_residual(Bs[l], AX[l], AP[l], states[l], R[l])    # R = B - (W x_old + a W p) = B - W x_new
+        elif full:
             mmv_all(X, AP)
             for l in range(L):
                 R[l].copy_(Bs[l])

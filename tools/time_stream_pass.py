@@ -10,9 +10,16 @@ the two things it is measured against:
              preconditioner chains on the side streams share the chip and the Infinity Cache: ms per pass from HIP events
              around every pass ("ktk" phase; the fold's two-vector passes included)
 
+  --nv N,..  instead of all of the above but the build: ktkn of N vectors on the streamed shard (odx_gauss_ktk_stream_h2n: one
+             build of K, the vectors in groups over the resident chunk) beside the composition it replaces, ceil(N / 2) calls
+             of the streamed ktk2 (a ktk for the odd one), alternating in one process, HIP events around each
+  --fit L,.. instead: odx.falkon_fit_path of L penalties (decades down from 1e-3) under "stream", seconds per fit
+
 Prints one JSON line per measurement (and writes them to --out when given).
     python tools/time_stream_pass.py --n 1000000 --D 1024 --M 10000
     python tools/time_stream_pass.py --n 5000000 --D 1024 --M 20000 --classes 1
+    python tools/time_stream_pass.py --n 1000000 --D 1024 --M 10000 --nv 4,8,16 --out profiles/stream_path.jsonl
+    python tools/time_stream_pass.py --n 1000000 --D 1024 --M 10000 --fit 4,8
 """
 import argparse
 import json
@@ -78,6 +85,9 @@ def main():
     ap.add_argument("--classes", type=int, default=2)
     ap.add_argument("--no-job", action="store_true")
     ap.add_argument("--no-compose", action="store_true")
+    ap.add_argument("--nv", default="", help="comma-separated vector counts: time ktkn on the streamed shard beside ktk2 / ktk calls")
+    ap.add_argument("--fit", default="", help="comma-separated path lengths: time falkon_fit_path under knm_storage 'stream'")
+    ap.add_argument("--tag", default=None, help="copied into every line (which tree was measured)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import bench
@@ -90,6 +100,8 @@ def main():
 
     def emit(d):
         d.update(n=n, D=D, M=M)
+        if a.tag:
+            d["tag"] = a.tag
         s = json.dumps(d)
         print(s, flush=True)
         lines.append(s)
@@ -106,6 +118,26 @@ def main():
     ring_bytes = int(be.lib.odx_gauss_ktk_stream_h2_workspace_bytes(n, M, D))
     emit({"what": "ring", "rows": R, "chunks": (n + R - 1) // R, "workspace_bytes": ring_bytes})
 
+    def finish():
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+
+    if a.fit:
+        y = torch.where((torch.arange(n, device=dev) % C) == 0, 1.0, -1.0).to(torch.float64)
+        with options.override(knm_storage="stream"):
+            for L in [int(x) for x in a.fit.split(",")]:
+                lams = [10.0 ** (-3 - 0.5 * i) for i in range(L)]
+
+                def fit():
+                    odx.falkon_fit_path(be, F, y, Zf, a.sigma, lams, 20)
+                fit()                                            # warm-up: workspaces, kernel load
+                torch.cuda.synchronize()
+                ms, every = _time(fit, a.reps)
+                emit({"what": "fit_path", "L": L, "s": ms / 1e3, "s_all": [x / 1e3 for x in every]})
+        finish()
+        return
+
     # stand-alone stored build of the same shape (scaled from a row slice when the block does not fit)
     rows = min(n, int(a.build_rows))
     Fs = F if rows == n else be.rows(F, torch.arange(rows, device=dev))
@@ -120,6 +152,37 @@ def main():
     del Fs
     torch.cuda.empty_cache()
     emit({"what": "build", "ms": build_ms * n / rows, "rows_timed": rows, "ms_timed": all_build})
+
+    if a.nv:
+        Mp = (M + 1) // 2 * 2
+        with options.override(knm_storage="stream"):
+            S, _ = be.knm_rhs(F, Zf, a.sigma, w)
+            Rn = int(be.lib.odx_gauss_ktk_stream_h2n_rows(M, D))
+            for nv in [int(x) for x in a.nv.split(",")]:
+                V = torch.randn((nv, Mp), generator=g, dtype=torch.float64).to(dev) * 1e-3
+                O, O2 = torch.zeros_like(V), torch.zeros_like(V)
+
+                def parent():
+                    for q in range(0, nv - 1, 2):
+                        be.ktk2(S, V[q, :M], V[q + 1, :M], out1=O2[q, :M], out2=O2[q + 1, :M])
+                    if nv % 2:
+                        be.ktk(S, v=V[nv - 1, :M], out=O2[nv - 1, :M])
+
+                def new():
+                    be.ktkn(S, V, out=O)
+                parent(), new()                                  # warm-up
+                torch.cuda.synchronize()
+                tp, tn = [], []
+                for _ in range(a.reps):                          # alternating: drift hits both alike
+                    tp.append(_time(parent, 1)[0])
+                    tn.append(_time(new, 1)[0])
+                mp, mn = statistics.median(tp), statistics.median(tn)
+                err = float((O - O2).abs().max() / O2.abs().max())
+                emit({"what": "ktkn_stream", "nv": nv, "rows": Rn, "chunks": (n + Rn - 1) // Rn, "ms": mn, "ms_all": tn,
+                      "parent_ms": mp, "parent_ms_all": tp, "vs_parent": mn / mp, "vs_build": mn / (build_ms * n / rows),
+                      "max_rel_diff": err})
+        finish()
+        return
 
     with options.override(knm_storage="stream"):
         S, _ = be.knm_rhs(F, Zf, a.sigma, w)
@@ -162,9 +225,7 @@ def main():
               "ms_per_pass_median": statistics.median(passes), "ms_knm_rhs_pass": statistics.median(timers["knm"].ms()),
               "ms_two_vector_pass": statistics.median(timers["ktk2"].ms()) if timers["ktk2"].ms() else None,
               "ms_score_mmv": statistics.median(timers["mmv"].ms()) if timers["mmv"].ms() else None})
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    finish()
 
 
 if __name__ == "__main__":
