@@ -188,6 +188,16 @@ int odx_knm_fwd_bwd(const float* K, int64_t ldk, int64_t n, int64_t M,
 int64_t odx_knm_fwd_bwd2_workspace_bytes(int64_t n, int64_t M);
 int odx_knm_fwd_bwd2(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* v2,
                      double* out, double* out2, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* The same passes with one more output: t_out (n f64, may be NULL) receives the row products t[r] = sum_j K[r, j] v[j] of
+ * the (first) vector, r < n, as the pass reduces them and BEFORE w is added — a by-product of phase 1, one 8-byte store
+ * per row.  With the directions v_i = T^-1 A^-1 p_i of a CG these are what the scores of the rows are made of:
+ * K alpha = sum_i a_i t_i (odx_cg_scores_axpy_f64).  `out` / `out2` are bit for bit what the calls above return, with or
+ * without t_out; t_out needs v.  Workspaces as for the calls above. */
+int odx_knm_fwd_bwd_t(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* w, double* out,
+                      double* t_out, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+int odx_knm_fwd_bwd2_t(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* v2,
+                       double* out, double* out2, double* t_out, void* workspace, int64_t workspace_bytes,
+                       odx_stream_t stream);
 
 /* Name of the kernel (as rocprofv3 lists it) a pass over a block of M columns stored as `fmt` launches, nv = 1 (one vector)
  * or 2 (two vectors from one read): the library's own dispatch rule, for tools that label measurements.  "" if no
@@ -222,6 +232,13 @@ int64_t odx_knm_fwd_bwd2_q_workspace_bytes(int64_t n, int64_t M, int fmt);
 int odx_knm_fwd_bwd2_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
                        const double* v, const double* v2, double* out, double* out2, void* workspace,
                        int64_t workspace_bytes, odx_stream_t stream);
+/* odx_knm_fwd_bwd_t / odx_knm_fwd_bwd2_t on the compact formats: t_out (n f64 or NULL) = K v of the (first) vector. */
+int odx_knm_fwd_bwd_q_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                        const double* v, const double* w, double* out, double* t_out, void* workspace,
+                        int64_t workspace_bytes, odx_stream_t stream);
+int odx_knm_fwd_bwd2_q_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                         const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
+                         int64_t workspace_bytes, odx_stream_t stream);
 /* out[q] = K' (K v[q]), q = 0 .. nv - 1, 3 <= nv <= 8, from ONE read of a compact-format block (what a lambda path's CG
  * states share: odx.solver.falkon_fit_path).  V / out: nv f64 rows, ldv / ldo doubles apart (even, >= M), 16-byte aligned.
  * The vectors sit in LDS as f64, so the widths that exist are nv <= 8 up to M = 2524 and nv <= 4 up to M = 5084; the
@@ -353,6 +370,12 @@ int odx_cg_finish(const double* R, double* P, double* state, double cg_eps, doub
  * (x_new = x_old + a p), both of which one odx_knm_fwd_bwd2 pass delivers; no-op once the stop flag is up. */
 int odx_cg_residual(const double* B, const double* AX, const double* AP, const double* state,
                     double* R, int64_t M, odx_stream_t stream);
+/* Scores of a shard's rows out of the CG itself.  odx_cg_scores_axpy_f64: S[i] += state[3] * t[i], i < n, nothing once the
+ * stop flag (state[2]) is up — odx_cg_step's guard; called between odx_cg_step and odx_cg_finish of an iteration with t = the
+ * t_out of that iteration's pass, S (zeroed by the caller before the first) ends as K alpha without another read of K.
+ * odx_cg_scores_store_f32: out[i * ldo] = (float) S[i] (one rounding, into a column of an (n, C) f32 matrix). */
+int odx_cg_scores_axpy_f64(const double* state, const double* t, double* S, int64_t n, odx_stream_t stream);
+int odx_cg_scores_store_f32(const double* S, int64_t n, float* out, int64_t ldo, odx_stream_t stream);
 /* y = a*x + b*y (f64), used for R = B - mmv(X) */
 int odx_axpby_f64(double a, const double* x, double b, double* y, int64_t M, odx_stream_t stream);
 

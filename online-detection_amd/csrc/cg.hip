@@ -138,6 +138,24 @@ __global__ __launch_bounds__(256) void cg_residual_kernel(const double* __restri
   if (i < M) R[i] = B[i] - fma(a, AP[i], AX[i]);
 }
 
+// S += a t over the n rows of a shard, a = state[3] (the step cg_step_kernel has just taken), nothing once the stop flag is
+// up — the guard of cg_step_body, so S receives exactly the steps X received: with t = K v of the step's direction
+// (v = T^-1 A^-1 p, the pass's t_out), S = K alpha when the loop ends.  n-sized: a grid-stride bandwidth kernel.
+__global__ __launch_bounds__(256) void cg_scores_axpy_kernel(const double* __restrict__ state, const double* __restrict__ t,
+                                                             double* __restrict__ S, int64_t n) {
+  if (state[2] != 0.0) return;
+  const double a = state[3];
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) S[i] = fma(a, t[i], S[i]);
+}
+
+// out[i * ldo] = (float) S[i]: the accumulated f64 scores rounded once into a column of the job's (n, C) f32 matrix
+__global__ __launch_bounds__(256) void cg_scores_store_kernel(const double* __restrict__ S, int64_t n, float* __restrict__ out,
+                                                              int64_t ldo) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) out[i * ldo] = (float)S[i];
+}
+
 __global__ __launch_bounds__(256) void axpby_kernel(double a, const double* __restrict__ x, double b,
                                                     double* __restrict__ y, int64_t M) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -215,6 +233,29 @@ extern "C" int odx_cg_residual(const double* B, const double* AX, const double* 
   hipLaunchKernelGGL(cg_residual_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, as_stream(stream), B, AX, AP,
                      state, R, M);
   ODX_CHECK_LAUNCH("odx_cg_residual");
+  return ODX_OK;
+}
+
+static unsigned rows_grid(int64_t n) {
+  int cus = odx_device_cus();
+  if (cus <= 0) cus = 256;
+  const int64_t want = ceil_div(n, 256), cap = (int64_t)cus * 8;
+  return (unsigned)(want < cap ? want : cap);
+}
+
+extern "C" int odx_cg_scores_axpy_f64(const double* state, const double* t, double* S, int64_t n, odx_stream_t stream) {
+  if (n <= 0) return ODX_OK;
+  ODX_REQUIRE(state && t && S, "odx_cg_scores_axpy_f64: null pointer");
+  hipLaunchKernelGGL(cg_scores_axpy_kernel, dim3(rows_grid(n)), dim3(256), 0, as_stream(stream), state, t, S, n);
+  ODX_CHECK_LAUNCH("odx_cg_scores_axpy_f64");
+  return ODX_OK;
+}
+
+extern "C" int odx_cg_scores_store_f32(const double* S, int64_t n, float* out, int64_t ldo, odx_stream_t stream) {
+  if (n <= 0) return ODX_OK;
+  ODX_REQUIRE(S && out && ldo >= 1, "odx_cg_scores_store_f32: null pointer or ldo < 1");
+  hipLaunchKernelGGL(cg_scores_store_kernel, dim3(rows_grid(n)), dim3(256), 0, as_stream(stream), S, n, out, ldo);
+  ODX_CHECK_LAUNCH("odx_cg_scores_store_f32");
   return ODX_OK;
 }
 

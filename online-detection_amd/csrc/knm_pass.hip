@@ -29,7 +29,7 @@ template <int NT, int CH, int R, int NV>
 __device__ __forceinline__ void knm_pass_body(const float* __restrict__ K, int64_t ldk, int64_t n, int64_t M,
                                               const double* __restrict__ v, const double* __restrict__ v2,
                                               const double* __restrict__ w, double* __restrict__ slab, int64_t slab_ld,
-                                              const int64_t wg, const int64_t nwg) {
+                                              double* __restrict__ t_out, const int64_t wg, const int64_t nwg) {
   constexpr int NW = NT / 64;
   constexpr int VCAP = (NT * CH * 4 < 20000) ? NT * CH * 4 : 20000;  // 160,000 B of the 163,840 B LDS at most
   constexpr bool VFULL = NV == 1 && NT * CH * 4 <= VCAP;             // v zero-filled up to every chunk a thread walks
@@ -133,6 +133,15 @@ __device__ __forceinline__ void knm_pass_body(const float* __restrict__ K, int64
 #pragma unroll
         for (int r = 0; r < R; ++r) t[q][r] = 0.0;
     }
+    // t_out: the row products K v of the (first) vector, as reduced and before w is added (scores summed from the CG's
+    // passes: K alpha = sum_i a_i K v_i).  Every thread holds them; one lane stores, outside the streaming part.
+    if (t_out != nullptr) {
+      if (tid == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (blk * R + r < n) t_out[blk * R + r] = t[0][r];
+      }
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int64_t row = blk * R + r;
@@ -183,8 +192,8 @@ template <int NT, int CH, int R, int NV>
 __global__ __launch_bounds__(NT) void knm_pass_kernel(const float* __restrict__ K, int64_t ldk, int64_t n, int64_t M,
                                                       const double* __restrict__ v, const double* __restrict__ v2,
                                                       const double* __restrict__ w, double* __restrict__ slab,
-                                                      int64_t slab_ld) {
-  knm_pass_body<NT, CH, R, NV>(K, ldk, n, M, v, v2, w, slab, slab_ld, blockIdx.x, gridDim.x);
+                                                      int64_t slab_ld, double* __restrict__ t_out) {
+  knm_pass_body<NT, CH, R, NV>(K, ldk, n, M, v, v2, w, slab, slab_ld, t_out, blockIdx.x, gridDim.x);
 }
 
 // The same pass for the classes of a batch (blockIdx.y = class): class b's block is walked by grid[b] workgroups exactly as
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(NT) void knm_pass_batched_kernel(PassBatch pb, cons
   const int b = blockIdx.y;
   if ((int)blockIdx.x >= pb.grid[b]) return;
   knm_pass_body<NT, CH, R, 1>(pb.K[b], pb.ldk[b], pb.n[b], pb.M[b], v + (int64_t)b * vstride, nullptr, nullptr,
-                              slab + (int64_t)b * slab_stride, slab_ld, blockIdx.x, pb.grid[b]);
+                              slab + (int64_t)b * slab_stride, slab_ld, nullptr, blockIdx.x, pb.grid[b]);
 }
 
 // Sum over the slabs g = wave, wave + 4, ... of one column (`stride` doubles from slab to slab): four loads in flight per
@@ -251,7 +260,7 @@ typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
 template <int NT, int CH, int R>
 __global__ __launch_bounds__(NT) void knm_pass2_kernel(const float* __restrict__ K, int64_t ldk, int64_t n, int64_t M,
                                                        const double* __restrict__ v1, const double* __restrict__ v2,
-                                                       double* __restrict__ slab, int64_t slab_ld) {
+                                                       double* __restrict__ slab, int64_t slab_ld, double* __restrict__ t_out) {
   constexpr int NW = NT / 64;
   extern __shared__ __attribute__((aligned(16))) double vs2[];       // [2][vcap]
   __shared__ double red[2][NW][2 * R];
@@ -345,6 +354,14 @@ __global__ __launch_bounds__(NT) void knm_pass2_kernel(const float* __restrict__
         t[q][r] = s;
       }
     pp ^= 1;
+    // t_out: the row products K v1 (rows past n read as zero and are not written); see knm_pass_body
+    if (t_out != nullptr) {
+      if (tid == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (blk * R + r < n) t_out[blk * R + r] = t[0][r];
+      }
+    }
     // The f32 -> f64 conversions of phase 1 must not stay live into phase 2 (the compiler would keep 2 x R x CH x 4
     // doubles beside the floats they came from and spill): an empty asm makes the K registers opaque here, so phase 2
     // converts again from the f32 registers (a quarter-rate VALU op on an HBM-bound kernel).
@@ -569,17 +586,18 @@ extern "C" int64_t odx_knm_fwd_bwd_workspace_bytes(int64_t n, int64_t M) {
 
 #define ODX_PASS_LAUNCH(NT_, CH_, R_)                                                                                \
   hipLaunchKernelGGL((knm_pass_kernel<NT_, CH_, R_, 1>), dim3(grid), dim3(NT_), 0, s, K, ldk, n, M, v, nullptr, w, \
-                     slab, slab_ld)
+                     slab, slab_ld, t_out)
 #define ODX_PASS2_LAUNCH(NT_, CH_, R_)                                                                                  \
   do {                                                                                                                  \
     ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_pass2_kernel<NT_, CH_, R_>),                    \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));                          \
     hipLaunchKernelGGL((knm_pass2_kernel<NT_, CH_, R_>), dim3(grid), dim3(NT_), lds2, s, K, ldk, n, M, v, v2, slab,   \
-                       slab_ld);                                                                                        \
+                       slab_ld, t_out);                                                                                 \
   } while (0)
 
-extern "C" int odx_knm_fwd_bwd(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* w,
-                               double* out, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+// (t_out: the _t entry's extra output, null for the plain one — same kernels, same slabs, same out either way)
+static int knm_fwd_bwd_impl(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* w, double* out,
+                            double* t_out, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
   ODX_REQUIRE(M > 0 && out, "odx_knm_fwd_bwd: M <= 0 or null out");
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
@@ -616,6 +634,17 @@ extern "C" int odx_knm_fwd_bwd(const float* K, int64_t ldk, int64_t n, int64_t M
   return ODX_OK;
 }
 
+extern "C" int odx_knm_fwd_bwd(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* w,
+                               double* out, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  return knm_fwd_bwd_impl(K, ldk, n, M, v, w, out, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_knm_fwd_bwd_t(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* w,
+                                 double* out, double* t_out, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(t_out == nullptr || v != nullptr, "odx_knm_fwd_bwd_t: t_out needs v");
+  return knm_fwd_bwd_impl(K, ldk, n, M, v, w, out, t_out, workspace, workspace_bytes, stream);
+}
+
 // ---------------------------------------------------------------- two products from one read of K
 // out = K' (K v), out2 = K' (K v2).  Supported where both vectors fit in LDS beside the reduction scratch and the
 // configuration's register budget allows a second set of column sums: 4096 < M <= 10 000 (the headline's M = 1e4 included);
@@ -638,9 +667,9 @@ extern "C" int64_t odx_knm_fwd_bwd2_workspace_bytes(int64_t n, int64_t M) {
   return 2 * odx_knm_fwd_bwd_workspace_bytes(n, M);
 }
 
-extern "C" int odx_knm_fwd_bwd2(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* v2,
-                                double* out, double* out2, void* workspace, int64_t workspace_bytes,
-                                odx_stream_t stream) {
+static int knm_fwd_bwd2_impl(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* v2,
+                             double* out, double* out2, double* t_out, void* workspace, int64_t workspace_bytes,
+                             odx_stream_t stream) {
   ODX_REQUIRE(M > 0 && out && out2, "odx_knm_fwd_bwd2: M <= 0 or null out");
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
@@ -672,4 +701,16 @@ extern "C" int odx_knm_fwd_bwd2(const float* K, int64_t ldk, int64_t n, int64_t 
                      out2);
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwd2(reduce)");
   return ODX_OK;
+}
+
+extern "C" int odx_knm_fwd_bwd2(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* v2,
+                                double* out, double* out2, void* workspace, int64_t workspace_bytes,
+                                odx_stream_t stream) {
+  return knm_fwd_bwd2_impl(K, ldk, n, M, v, v2, out, out2, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_knm_fwd_bwd2_t(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* v2,
+                                  double* out, double* out2, double* t_out, void* workspace, int64_t workspace_bytes,
+                                  odx_stream_t stream) {
+  return knm_fwd_bwd2_impl(K, ldk, n, M, v, v2, out, out2, t_out, workspace, workspace_bytes, stream);
 }

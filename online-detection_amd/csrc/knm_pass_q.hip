@@ -30,7 +30,7 @@ __device__ __forceinline__ void knm_passq_body(const unsigned short* __restrict_
                                                const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                int64_t M, const double* __restrict__ v1, const double* __restrict__ v2,
                                                const double* __restrict__ w, double* __restrict__ slab, int64_t slab_ld,
-                                               int wg, int nwg) {
+                                               double* __restrict__ t_out, int wg, int nwg) {
   constexpr int NW = NT / 64;
   constexpr int CW = QCW;
   extern __shared__ __attribute__((aligned(16))) double vsq[];       // [NV][vcap]
@@ -146,6 +146,15 @@ __device__ __forceinline__ void knm_passq_body(const unsigned short* __restrict_
         }
       pp ^= 1;
     }
+    // t_out: the row products K v of the (first) vector, as reduced and before w is added — what a caller sums into scores
+    // (K alpha = sum_i a_i K v_i over the CG's steps).  Every thread holds them; one lane stores, outside the streaming part.
+    if (t_out != nullptr) {
+      if (tid == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (blk * R + r < n) t_out[blk * R + r] = t[0][r];
+      }
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int64_t row = blk * R + r;
@@ -206,8 +215,9 @@ template <int NT, int CH, int R, int NV, int FMT, int WPE>
 __global__ __launch_bounds__(NT, WPE) void knm_passq_kernel(const unsigned short* __restrict__ Khi, int64_t ldk,
                                                        const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                        int64_t M, const double* __restrict__ v1, const double* __restrict__ v2,
-                                                       const double* __restrict__ w, double* __restrict__ slab, int64_t slab_ld) {
-  knm_passq_body<NT, CH, R, NV, FMT, WPE>(Khi, ldk, Klo, ldlo, n, M, v1, v2, w, slab, slab_ld, (int)blockIdx.x, (int)gridDim.x);
+                                                       const double* __restrict__ w, double* __restrict__ slab, int64_t slab_ld,
+                                                       double* __restrict__ t_out) {
+  knm_passq_body<NT, CH, R, NV, FMT, WPE>(Khi, ldk, Klo, ldlo, n, M, v1, v2, w, slab, slab_ld, t_out, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The classes of a batch by one launch (blockIdx.y = class): class b's block is walked by grid[b] workgroups exactly as its
@@ -229,7 +239,7 @@ __global__ __launch_bounds__(NT, WPE) void knm_passq_batched_kernel(PassBatchQ p
   const int b = blockIdx.y;
   if ((int)blockIdx.x >= pb.grid[b]) return;
   knm_passq_body<NT, CH, R, 1, FMT, WPE>(pb.Khi[b], pb.ldk[b], pb.Klo[b], pb.ldlo[b], pb.n[b], pb.M[b], v + (int64_t)b * vstride, nullptr,
-                                         nullptr, slab + (int64_t)b * slab_stride, slab_ld, (int)blockIdx.x, pb.grid[b]);
+                                         nullptr, slab + (int64_t)b * slab_stride, slab_ld, nullptr, (int)blockIdx.x, pb.grid[b]);
 }
 
 // ---------------------------------------------------------------- two free-running halves (one vector, 8192 < M <= 10240)
@@ -250,7 +260,7 @@ __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __rest
                                                     const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                     int64_t M, const double* __restrict__ v1,
                                                     const double* __restrict__ w, double* __restrict__ slab,
-                                                    int64_t slab_ld, int wg, int nwg) {
+                                                    int64_t slab_ld, double* __restrict__ t_out, int wg, int nwg) {
   constexpr int NT = 256, CW = QCW;
   extern __shared__ __attribute__((aligned(16))) double vsq[];
   __shared__ double red[2][2][4][R];                 // [half][ping-pong][wave of the half][row]
@@ -369,6 +379,17 @@ __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __rest
           if (FMT == QF_U24) asm volatile("" : "+v"(kr[r][c].lo[0]));
         }
     }
+    // t_out: this half's row products K v, as reduced and before w is added (see knm_passq_body).  The branch is wave-uniform
+    // (kernel argument, hw from readfirstlane): with a null t_out the trip is the one without it plus one scalar compare.  The
+    // store is issued when the block's loads have all been consumed and before the next block's are re-issued, so every
+    // vmcnt wait on those loads is already past it.
+    if (t_out != nullptr && hw == 0) {
+      if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (blk * R + r < n) t_out[blk * R + r] = t[r];
+      }
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int64_t row = blk * R + r;
@@ -407,8 +428,8 @@ __global__ __launch_bounds__(512, 2) void knm_passq_stag_kernel(const unsigned s
                                                                 const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                                 int64_t M, const double* __restrict__ v1,
                                                                 const double* __restrict__ w, double* __restrict__ slab,
-                                                                int64_t slab_ld) {
-  knm_passq_stag_body<CH, R, FMT>(Khi, ldk, Klo, ldlo, n, M, v1, w, slab, slab_ld, (int)blockIdx.x, (int)gridDim.x);
+                                                                int64_t slab_ld, double* __restrict__ t_out) {
+  knm_passq_stag_body<CH, R, FMT>(Khi, ldk, Klo, ldlo, n, M, v1, w, slab, slab_ld, t_out, (int)blockIdx.x, (int)gridDim.x);
 }
 
 template <int CH, int R, int FMT>
@@ -418,7 +439,7 @@ __global__ __launch_bounds__(512, 2) void knm_passq_stag_batched_kernel(PassBatc
   const int b = blockIdx.y;
   if ((int)blockIdx.x >= pb.grid[b]) return;
   knm_passq_stag_body<CH, R, FMT>(pb.Khi[b], pb.ldk[b], pb.Klo[b], pb.ldlo[b], pb.n[b], pb.M[b], v + (int64_t)b * vstride, nullptr,
-                                  slab + (int64_t)b * slab_stride, slab_ld, (int)blockIdx.x, pb.grid[b]);
+                                  slab + (int64_t)b * slab_stride, slab_ld, nullptr, (int)blockIdx.x, pb.grid[b]);
 }
 
 struct QCfg {
@@ -479,19 +500,19 @@ static int qgrid_for(const QCfg& cfg, int64_t n) {
 
 template <int NT, int CH, int R, int NV, int FMT, int WPE = (NT >= 1024 ? 4 : 2)>
 static int launch_passq(int grid, size_t lds, hipStream_t s, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int64_t n,
-                        int64_t M, const double* v, const double* v2, const double* w, double* slab, int64_t slab_ld) {
+                        int64_t M, const double* v, const double* v2, const double* w, double* slab, int64_t slab_ld, double* t_out) {
   ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_passq_kernel<NT, CH, R, NV, FMT, WPE>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((knm_passq_kernel<NT, CH, R, NV, FMT, WPE>), dim3(grid), dim3(NT), lds, s, static_cast<const unsigned short*>(K),
-                     ldk, static_cast<const unsigned char*>(Klo), ldlo, n, M, v, v2, w, slab, slab_ld);
+                     ldk, static_cast<const unsigned char*>(Klo), ldlo, n, M, v, v2, w, slab, slab_ld, t_out);
   return ODX_OK;
 }
 
 template <int NV, int FMT>
 static int dispatch_passq(const QCfg& cfg, int grid, size_t lds, hipStream_t s, const void* K, int64_t ldk, const void* Klo,
                           int64_t ldlo, int64_t n, int64_t M, const double* v, const double* v2, const double* w, double* slab,
-                          int64_t slab_ld) {
-#define ODX_Q(NT_, CH_, R_) return launch_passq<NT_, CH_, R_, NV, FMT>(grid, lds, s, K, ldk, Klo, ldlo, n, M, v, v2, w, slab, slab_ld)
+                          int64_t slab_ld, double* t_out) {
+#define ODX_Q(NT_, CH_, R_) return launch_passq<NT_, CH_, R_, NV, FMT>(grid, lds, s, K, ldk, Klo, ldlo, n, M, v, v2, w, slab, slab_ld, t_out)
   if constexpr (NV == 1) {
     if (cfg.nt == 0) {
 #define ODX_QH(CH_, R_)                                                                                                         \
@@ -500,7 +521,7 @@ static int dispatch_passq(const QCfg& cfg, int grid, size_t lds, hipStream_t s, 
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                   \
     hipLaunchKernelGGL((knm_passq_stag_kernel<CH_, R_, FMT>), dim3(grid), dim3(512), lds, s,                                    \
                        static_cast<const unsigned short*>(K), ldk, static_cast<const unsigned char*>(Klo), ldlo, n, M, v, w,    \
-                       slab, slab_ld);                                                                                          \
+                       slab, slab_ld, t_out);                                                                                   \
     return ODX_OK;                                                                                                              \
   } while (0)
       if (cfg.ch == 2) ODX_QH(2, 8);
@@ -678,9 +699,10 @@ extern "C" int64_t odx_knm_fwd_bwd_q_workspace_bytes(int64_t n, int64_t M, int f
   return (int64_t)cus * (cfg.nt == 0 ? 2 * cfg.wg_per_cu : cfg.wg_per_cu) * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
-extern "C" int odx_knm_fwd_bwd_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
-                                 const double* v, const double* w, double* out, void* workspace, int64_t workspace_bytes,
-                                 odx_stream_t stream) {
+// (t_out: the _t entry's extra output, null for the plain one — same kernels, same slabs, same out either way)
+static int knm_fwd_bwd_q_impl(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                              const double* v, const double* w, double* out, double* t_out, void* workspace,
+                              int64_t workspace_bytes, odx_stream_t stream) {
   ODX_REQUIRE(M > 0 && out, "odx_knm_fwd_bwd_q: M <= 0 or null out");
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
@@ -704,10 +726,23 @@ extern "C" int odx_knm_fwd_bwd_q(const void* K, int64_t ldk, const void* Klo, in
   double* slab = static_cast<double*>(workspace);
   // (the halves kernel keeps v zero-filled up to the 10 x 256 chunks of four its threads walk)
   const size_t lds = (cfg.nt == 0 ? (size_t)(cfg.ch * 256 * 4) : (size_t)(slab_ld + 4)) * sizeof(double);      // + the zero chunk
-  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_passq<1, QF_U24>(cfg, grid, lds, s, K, ldk, Klo, ldlo, n, M, v, nullptr, w, slab, slab_ld)));
-  else ODX_PROPAGATE((dispatch_passq<1, QF_BF16>(cfg, grid, lds, s, K, ldk, nullptr, 0, n, M, v, nullptr, w, slab, slab_ld)));
+  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_passq<1, QF_U24>(cfg, grid, lds, s, K, ldk, Klo, ldlo, n, M, v, nullptr, w, slab, slab_ld, t_out)));
+  else ODX_PROPAGATE((dispatch_passq<1, QF_BF16>(cfg, grid, lds, s, K, ldk, nullptr, 0, n, M, v, nullptr, w, slab, slab_ld, t_out)));
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwd_q");
   return slab_reduce_f64(slab, slab_ld, nslab, M, out, s);
+}
+
+extern "C" int odx_knm_fwd_bwd_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                 const double* v, const double* w, double* out, void* workspace, int64_t workspace_bytes,
+                                 odx_stream_t stream) {
+  return knm_fwd_bwd_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, w, out, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_knm_fwd_bwd_q_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                   const double* v, const double* w, double* out, double* t_out, void* workspace,
+                                   int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(t_out == nullptr || v != nullptr, "odx_knm_fwd_bwd_q_t: t_out needs v");
+  return knm_fwd_bwd_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, w, out, t_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t odx_knm_fwd_bwd2_q_workspace_bytes(int64_t n, int64_t M, int fmt) {
@@ -719,9 +754,9 @@ extern "C" int64_t odx_knm_fwd_bwd2_q_workspace_bytes(int64_t n, int64_t M, int 
   return 2 * (int64_t)cus * cfg.wg_per_cu * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
-extern "C" int odx_knm_fwd_bwd2_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
-                                  const double* v, const double* v2, double* out, double* out2, void* workspace,
-                                  int64_t workspace_bytes, odx_stream_t stream) {
+static int knm_fwd_bwd2_q_impl(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                               const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
+                               int64_t workspace_bytes, odx_stream_t stream) {
   ODX_REQUIRE(M > 0 && out && out2, "odx_knm_fwd_bwd2_q: M <= 0 or null out");
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
@@ -744,8 +779,20 @@ extern "C" int odx_knm_fwd_bwd2_q(const void* K, int64_t ldk, const void* Klo, i
   }
   double* slab = static_cast<double*>(workspace);
   const size_t lds = (size_t)(2 * (slab_ld + 4) * sizeof(double));      // two vectors, each with its zero chunk
-  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_passq<2, QF_U24>(cfg, grid, lds, s, K, ldk, Klo, ldlo, n, M, v, v2, nullptr, slab, slab_ld)));
-  else ODX_PROPAGATE((dispatch_passq<2, QF_BF16>(cfg, grid, lds, s, K, ldk, nullptr, 0, n, M, v, v2, nullptr, slab, slab_ld)));
+  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_passq<2, QF_U24>(cfg, grid, lds, s, K, ldk, Klo, ldlo, n, M, v, v2, nullptr, slab, slab_ld, t_out)));
+  else ODX_PROPAGATE((dispatch_passq<2, QF_BF16>(cfg, grid, lds, s, K, ldk, nullptr, 0, n, M, v, v2, nullptr, slab, slab_ld, t_out)));
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwd2_q");
   return slab_reduce2_f64(slab, slab_ld, grid, M, out, out2, s);
+}
+
+extern "C" int odx_knm_fwd_bwd2_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                  const double* v, const double* v2, double* out, double* out2, void* workspace,
+                                  int64_t workspace_bytes, odx_stream_t stream) {
+  return knm_fwd_bwd2_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, v2, out, out2, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_knm_fwd_bwd2_q_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                    const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
+                                    int64_t workspace_bytes, odx_stream_t stream) {
+  return knm_fwd_bwd2_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, v2, out, out2, t_out, workspace, workspace_bytes, stream);
 }

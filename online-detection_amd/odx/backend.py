@@ -562,10 +562,21 @@ class HipBackend(PathOps):
                                                    _p(Zf.meta), _p(Zf.sq), K.M, F.D, K.sigma, _p(v), _p(v2), _p(w), _p(out),
                                                    _p(out2), _p(ws), ws.numel(), self._stream()), "odx_gauss_ktk_stream_h2")
 
-    def ktk(self, K, v=None, w=None, out=None):
-        """out = K' (K v + w) over this shard (f64)."""
+    def _check_t_out(self, K, v, t_out):
+        if K.fmt == "stream":
+            raise ValueError("ktk: t_out needs a stored K_nM block (a streamed shard's rows pass in chunks)")
+        if v is None:
+            raise ValueError("ktk: t_out is the row product K v: it needs v")
+        if t_out.dtype != torch.float64 or t_out.numel() != K.n or not t_out.is_contiguous():
+            raise ValueError("ktk: t_out must be a contiguous f64 vector of the block's %d rows" % K.n)
+
+    def ktk(self, K, v=None, w=None, out=None, t_out=None):
+        """out = K' (K v + w) over this shard (f64).  t_out: optional (n,) f64 that receives the row products K v (before w
+        is added), a by-product of the same read of K (odx_knm_fwd_bwd[_q]_t); `out` is bitwise the same with or without it."""
         if out is None:
             out = torch.empty(K.M, dtype=torch.float64, device=self.device)
+        if t_out is not None:
+            self._check_t_out(K, v, t_out)
         if K.fmt == "stream":
             self._ktk_stream(K, v, None, w, out, None)
             return out
@@ -575,6 +586,10 @@ class HipBackend(PathOps):
             if nbytes < 0:
                 raise hip.OdxError("odx_knm_fwd_bwd_q: M = %d is outside the supported range" % K.M)
             ws = self._workspace("ktk", nbytes)
+            if t_out is not None:
+                hip.check(self.lib.odx_knm_fwd_bwd_q_t(_p(K.K), K.ld, _p(K.lo), K.ld, code, K.n, K.M, _p(v), _p(w), _p(out), _p(t_out),
+                                                       _p(ws), ws.numel(), self._stream()), "odx_knm_fwd_bwd_q_t")
+                return out
             hip.check(self.lib.odx_knm_fwd_bwd_q(_p(K.K), K.ld, _p(K.lo), K.ld, code, K.n, K.M, _p(v), _p(w), _p(out), _p(ws),
                                                  ws.numel(), self._stream()), "odx_knm_fwd_bwd_q")
             return out
@@ -582,6 +597,10 @@ class HipBackend(PathOps):
         if nbytes < 0:
             raise hip.OdxError("odx_knm_fwd_bwd: M = %d is outside the supported range" % K.M)
         ws = self._workspace("ktk", nbytes)
+        if t_out is not None:
+            hip.check(self.lib.odx_knm_fwd_bwd_t(_p(K.K), K.ld, K.n, K.M, _p(v), _p(w), _p(out), _p(t_out), _p(ws), ws.numel(),
+                                                 self._stream()), "odx_knm_fwd_bwd_t")
+            return out
         hip.check(self.lib.odx_knm_fwd_bwd(_p(K.K), K.ld, K.n, K.M, _p(v), _p(w), _p(out), _p(ws), ws.numel(),
                                            self._stream()), "odx_knm_fwd_bwd")
         return out
@@ -596,8 +615,11 @@ class HipBackend(PathOps):
         shard always has one: each chunk is built once and read for both vectors while it is resident."""
         return K.fmt == "stream" or self._ktk2_bytes(K) >= 0
 
-    def ktk2(self, K, v1, v2, out1=None, out2=None):
-        """out1 = K' (K v1), out2 = K' (K v2) over this shard from ONE read of K (odx_knm_fwd_bwd2[_q])."""
+    def ktk2(self, K, v1, v2, out1=None, out2=None, t_out=None):
+        """out1 = K' (K v1), out2 = K' (K v2) over this shard from ONE read of K (odx_knm_fwd_bwd2[_q]).  t_out: optional
+        (n,) f64 that receives the row products K v1 (odx_knm_fwd_bwd2[_q]_t)."""
+        if t_out is not None:
+            self._check_t_out(K, v1, t_out)
         if out1 is None:
             out1 = torch.empty(K.M, dtype=torch.float64, device=self.device)
         if out2 is None:
@@ -609,6 +631,15 @@ class HipBackend(PathOps):
         if nbytes < 0:
             raise hip.OdxError("odx_knm_fwd_bwd2: M = %d is outside the two-vector configurations" % K.M)
         ws = self._workspace("ktk", nbytes)
+        if t_out is not None:
+            if K.fmt != "f32":
+                hip.check(self.lib.odx_knm_fwd_bwd2_q_t(_p(K.K), K.ld, _p(K.lo), K.ld, _KNM_CODE[K.fmt], K.n, K.M, _p(v1), _p(v2),
+                                                        _p(out1), _p(out2), _p(t_out), _p(ws), ws.numel(), self._stream()),
+                          "odx_knm_fwd_bwd2_q_t")
+            else:
+                hip.check(self.lib.odx_knm_fwd_bwd2_t(_p(K.K), K.ld, K.n, K.M, _p(v1), _p(v2), _p(out1), _p(out2), _p(t_out), _p(ws),
+                                                      ws.numel(), self._stream()), "odx_knm_fwd_bwd2_t")
+            return out1, out2
         if K.fmt != "f32":
             hip.check(self.lib.odx_knm_fwd_bwd2_q(_p(K.K), K.ld, _p(K.lo), K.ld, _KNM_CODE[K.fmt], K.n, K.M, _p(v1), _p(v2),
                                                   _p(out1), _p(out2), _p(ws), ws.numel(), self._stream()), "odx_knm_fwd_bwd2_q")
@@ -620,6 +651,20 @@ class HipBackend(PathOps):
     def cg_residual(self, B, AX, AP, state, R):
         """R = B - (AX + a AP), a = the step cg_step has just taken (state[3])."""
         hip.check(self.lib.odx_cg_residual(_p(B), _p(AX), _p(AP), _p(state), _p(R), R.numel(), self._stream()), "odx_cg_residual")
+
+    def cg_scores_axpy(self, state, t, S):
+        """S += a t over a shard's rows, a = the step cg_step has just taken (state[3]); nothing once the stop flag is up.
+        With t = the t_out of the iteration's pass, S ends as K alpha (odx_cg_scores_axpy_f64)."""
+        if S.dtype != torch.float64 or t.dtype != torch.float64 or S.numel() != t.numel() or not (S.is_contiguous() and t.is_contiguous()):
+            raise ValueError("cg_scores_axpy: t and S must be contiguous f64 vectors of the same length")
+        hip.check(self.lib.odx_cg_scores_axpy_f64(_p(state), _p(t), _p(S), S.numel(), self._stream()), "odx_cg_scores_axpy_f64")
+
+    def cg_scores_store(self, S, out):
+        """out (n,) or (n, 1) f32, possibly a strided column such as scores[:, c:c + 1], = (float) S (odx_cg_scores_store_f32)."""
+        if out.dtype != torch.float32 or out.shape[0] != S.numel() or (out.dim() == 2 and out.shape[1] != 1) or S.dtype != torch.float64:
+            raise ValueError("cg_scores_store: S must be (n,) f64 and out an (n,) or (n, 1) f32 tensor")
+        hip.check(self.lib.odx_cg_scores_store_f32(_p(S), S.numel(), _p(out), out.stride(0), self._stream()), "odx_cg_scores_store_f32")
+        return out
 
     def cg_solve(self, K, P, b0, n_total, lam, maxiter, opt):
         """The CG loop of an unsharded fit in one library call (odx_falkon_cg_f64); returns alpha (M,) f64.  f32-stored
@@ -716,11 +761,19 @@ class HipBackend(PathOps):
         hip.check(self.lib.odx_axpby_f64(float(a), _p(x), float(b), _p(y), y.numel(), self._stream()), "odx_axpby_f64")
 
     # ------------------------------------------------------------------ scoring
-    def knm_mv(self, K, alpha, out=None):
+    def knm_mv(self, K, alpha, out=None, summed=None):
         """(n, 1) f32 = K alpha over a stored K_nM block, from one read of it (odx_knm_mv; f64 sums); `out` may be a
-        strided column such as scores[:, c:c + 1]."""
+        strided column such as scores[:, c:c + 1].  summed: the caller already holds K alpha as an (n,) f64 vector — the fit
+        that produced alpha summed it from its passes' row products (solver.falkon_fit(scores_out=...)) — and the block is
+        not read again: the sum is rounded once into `out` (odx_cg_scores_store_f32)."""
         if K.fmt not in _KNM_CODE:
             raise ValueError("knm_mv: needs a stored K_nM block, got %r (a streamed shard is scored by mmv)" % (K.fmt,))
+        if summed is not None:
+            if summed.numel() != K.n:
+                raise ValueError("knm_mv: summed has %d entries but the block has %d rows" % (summed.numel(), K.n))
+            if out is None:
+                out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
+            return self.cg_scores_store(summed, out)
         alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
         if alpha.numel() != K.M:
             raise ValueError("knm_mv: alpha has %d entries but the block has %d columns" % (alpha.numel(), K.M))

@@ -97,7 +97,7 @@ class LockstepClassJob:
     def __init__(self, be, X, n_total, M, labels, centre_idx, sigma, lam, maxiter=20, opt=None, shard=None,
                  precond_batch=0, precond_depth=2, precond_after_fit=False, classes=None, precond_cus=0, batch=0,
                  hbm_bytes=None, exchange="lockstep", gauss_on_complement=False, precond_lookahead=1, precond_cus_full_only=False,
-                 score_from_knm=True):
+                 score_from_knm=True, scores_from_cg=True):
         """precond_batch: classes per rank and preconditioner chain (g; 0 = planned, 1 = one chain per class on `precond_depth`
         side streams); batch: classes per lock-step batch (b, a divisor of the world size; 0 = planned); hbm_bytes: the
         memory the plan may count on per rank (default: the device's, 288 GB without one).
@@ -106,7 +106,10 @@ class LockstepClassJob:
         classes one at a time, EVERY rank builds every class's preconditioner and runs every M-sized product, per CG iteration
         ONE all-reduce of the (M,) partial (solver.falkon_fit's replicated mode).  Same arithmetic per class either way.
         score_from_knm: score a class from the K_nM shard its fit has just stored (one read of it, backend.knm_mv) where
-        that shard holds the f32-accurate entries (see _score); False: always recompute K(X, Z) alpha (backend.mmv)."""
+        that shard holds the f32-accurate entries (see _score); False: always recompute K(X, Z) alpha (backend.mmv).
+        scores_from_cg: where this rank holds the CG state of a class (one rank, or exchange "allreduce") and that shard
+        qualifies (solver.scores_from_cg), sum the scores from the row products of the CG's own passes and hand the sum to
+        knm_mv, which then does not read the shard again; with score_from_knm off, or on several lock-step ranks, it has no effect."""
         # gauss_on_complement (with precond_cus = k > 0; an experiment, round-5 review item 1a): the K_nM builds and the scoring run
         # on a stream confined to the OTHER total - k compute units, so that chain and Gaussian workgroups never share a CU.
         # precond_lookahead = L: chain groups in flight ahead of the group being fitted (L + 1 factor blocks; 1 = round 2-5's
@@ -118,6 +121,7 @@ class LockstepClassJob:
             raise ValueError("LockstepClassJob: exchange must be 'lockstep' or 'allreduce', got %r" % (exchange,))
         self.exchange = exchange
         self.score_from_knm = bool(score_from_knm)
+        self.scores_from_cg = bool(scores_from_cg) and self.score_from_knm
         if exchange == "allreduce":
             batch = 1                             # one stored K_nM shard in flight; the plan's b = 1 line is this mode's memory
         self.be, self.X, self.N, self.M = be, X, int(n_total), int(M)
@@ -149,6 +153,10 @@ class LockstepClassJob:
             if hasattr(be, "knm_bytes") else self.n_loc * self.ldk * 4
         self.kbufs = [torch.empty(max(kbytes, 16), dtype=torch.uint8, device=dev) for _ in range(self.b)]
         self.scores = torch.empty((self.n_loc, self.C), dtype=torch.float32, device=dev)
+        # the f64 sum of a class's scores while its CG runs (scores_from_cg); rounded once into its column of `scores`
+        self.sbuf = (torch.empty(self.n_loc, dtype=torch.float64, device=dev)
+                     if self.scores_from_cg and (self.shard.world == 1 or exchange == "allreduce") and hasattr(be, "cg_scores_axpy")
+                     else None)
         self.depth = precond_depth if precond_depth > 0 else 2
         self.after_fit = bool(precond_after_fit)
         self.ld_p = (self.M + 1) // 2 * 2
@@ -184,7 +192,7 @@ class LockstepClassJob:
                         be._workspace("precond_group", be.lib.odx_falkon_precond_batched_workspace_bytes(self.M, D, self.G))
 
     def release(self):
-        self.kbufs, self.pbuf, self.pgroup, self.scores = [], [], [], None
+        self.kbufs, self.pbuf, self.pgroup, self.scores, self.sbuf = [], [], [], None, None
 
     # ------------------------------------------------------------------ pieces
     def _centre_plan(self, idx):
@@ -235,14 +243,18 @@ class LockstepClassJob:
         self.shard.gather_blocks(blk, allb)
         return be.features(allb.view(self.world * cmax, X.shape[1]).index_select(0, slot))
 
-    def _score(self, ph, F, Z, K, alpha, c):
-        """scores[:, c] = K(X, Z) alpha.  From the stored shard K the fit has just streamed when its entries are the Gaussian's
-        f32-accurate values (gauss "h2", stored as 24-bit fixed point or f32): one HBM-bound read of it, timed with the passes
+    def _score(self, ph, F, Z, K, alpha, c, summed=False):
+        """scores[:, c] = K(X, Z) alpha.  summed: the fit has left K alpha in self.sbuf (f64, summed from the row products
+        of its CG passes: solver.scores_from_cg) — backend.knm_mv then rounds that sum into the column, no read of K.  Otherwise from the
+        stored shard K the fit has just streamed when its entries are the Gaussian's f32-accurate values (gauss "h2", stored as 24-bit fixed point or f32): one HBM-bound read of it, timed with the passes
         ("ktk"), instead of a second 2 n M D contraction.  bf16 / f8 shards are ~1e-3 off, so their scores (and those of a
         backend without knm_mv) are recomputed by the contraction.  The next batch's build overwrites K only after this
         launch, in stream order."""
         be = self.be
-        if (self.score_from_knm and K is not None and hasattr(be, "knm_mv") and getattr(be, "gauss", None) == "h2"
+        if summed:
+            # (outside the "ktk" timer: an n-sized rounding, not a read of the block)
+            be.knm_mv(K, alpha, out=self.scores[:, c:c + 1], summed=self.sbuf)
+        elif (self.score_from_knm and K is not None and hasattr(be, "knm_mv") and getattr(be, "gauss", None) == "h2"
                 and getattr(K, "fmt", None) in ("u24", "f32")):
             with ph("ktk"):
                 be.knm_mv(K, alpha, out=self.scores[:, c:c + 1])
@@ -345,10 +357,11 @@ class LockstepClassJob:
             alpha = solver.falkon_fit(be, F, self.labels(c), Z, self.sigma, self.lam, self.maxiter, self.opt, n_total=self.N,
                                       shard=self.shard, owner=None, knm_out=self.kbufs[0],
                                       phase=(lambda name: phases[name]) if phases is not None else None,
-                                      precond=P, precond_ready=(lambda ev=ev: _wait(ev)), knm_blocks=Ks)
+                                      precond=P, precond_ready=(lambda ev=ev: _wait(ev)), knm_blocks=Ks, scores_out=self.sbuf)
             if alphas_out is not None:
                 alphas_out[c] = alpha
-            self._score(ph, F, Z, Ks[0] if Ks else None, alpha, c)
+            self._score(ph, F, Z, Ks[0] if Ks else None, alpha, c,
+                        summed=self.sbuf is not None and bool(Ks) and solver.scores_from_cg(be, Ks[0]))
             out = (alpha, Z)
         if hasattr(be, "release_helper_streams"):
             be.release_helper_streams()
@@ -399,15 +412,17 @@ class LockstepClassJob:
                                                 shard=self.shard, knm_outs=self.kbufs[:len(batch)],
                                                 phase=ph if (phases is not None or self.gauss_stream is not None) else None,
                                                 precond=P if mine else None,
-                                                precond_ready=(lambda: _wait(ev)) if mine else None, owners=owners, knm_blocks=Ks)
+                                                precond_ready=(lambda: _wait(ev)) if mine else None, owners=owners, knm_blocks=Ks,
+                                                scores_out=[self.sbuf] if (self.sbuf is not None and len(batch) == 1) else None)
             if self.G == 1 and self.after_fit and bi + self.depth < len(sched):
                 # issued behind this batch's CG in stream order: the factorisations then run beside the MFMA-bound scoring
                 # of this batch and K_nM build of the next, and the HBM-bound passes keep the chip to themselves
                 ready[bi + self.depth] = self._prepare(*sched[bi + self.depth], (bi + self.depth) % self.nslot, ph, infos)
             if alphas_out is not None:
                 alphas_out.update((c, alphas[pos]) for pos, c in enumerate(batch))
+            summed = self.sbuf is not None and len(batch) == 1 and len(Ks) == 1 and solver.scores_from_cg(be, Ks[0])
             for pos, c in enumerate(batch):
-                self._score(ph, F, Zs[pos], Ks[pos] if pos < len(Ks) else None, alphas[pos], c)
+                self._score(ph, F, Zs[pos], Ks[pos] if pos < len(Ks) else None, alphas[pos], c, summed=summed)
             out = (alphas[-1], Zs[-1])
         if hasattr(be, "release_helper_streams"):
             # the chains' internal helper streams go when the step is queued (their work completes first; the next step's first

@@ -76,8 +76,22 @@ def _can_fold(be, K, M, rows_per_rank):
     return bool(getattr(K, "fmt", None) == "stream" or rows_per_rank >= 8 * M)
 
 
+def scores_from_cg(be, K):
+    """Whether a fit over the stored block K can hand back the scores K alpha of its rows as a by-product of its CG passes.
+
+    alpha = T^-1 A^-1 x and x = sum_i a_i p_i over the steps taken; the vector pass i multiplies K with is
+    v_i = T^-1 A^-1 p_i, so K alpha = sum_i a_i (K v_i), and K v_i is phase 1 of the pass (its t_out): no further read of K
+    (backend.knm_mv reads the whole block once more for the same sum).  Needs the backend's t_out passes and n-sized score
+    kernels, and a block whose entries are the Gaussian's f32-accurate values (gauss "h2" stored as 24-bit fixed point or
+    f32: the blocks LockstepClassJob._score reads with knm_mv); streamed shards, bf16 / f8 blocks and other backends do not
+    qualify."""
+    return bool(hasattr(be, "cg_scores_axpy") and hasattr(be, "cg_scores_store") and getattr(be, "gauss", None) == "h2"
+                and getattr(K, "fmt", None) in ("u24", "f32"))
+
+
 def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, allreduce=None, knm_out=None,
-               return_knm=False, phase=None, precond=None, shard=None, owner=None, precond_ready=None, knm_blocks=None):
+               return_knm=False, phase=None, precond=None, shard=None, owner=None, precond_ready=None, knm_blocks=None,
+               scores_out=None):
     """Fit one binary FALKON problem.
 
     be        backend (odx.backend.HipBackend in the product)
@@ -106,6 +120,11 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     knm_blocks
               optional list that receives the K_nM block this fit built (the stored shard its passes
               streamed: the caller can score from it)
+    scores_out
+              optional (n_local,) f64 device vector: where scores_from_cg(be, K) holds and this rank holds the CG state
+              (one shard, or replicated row shards: not the owner mode), it is zeroed and receives K alpha for this rank's
+              rows, summed step by step from the passes' row products; otherwise it is left untouched (the caller asks
+              scores_from_cg about the block it gets through knm_blocks)
     returns   alpha (M,) f64 device vector (on every rank)
     """
     opt = opt or SolverOptions()
@@ -133,16 +152,23 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
             r = be.ktk(K, **kw)
         return ar(r)
 
+    # scores as a by-product (see scores_from_cg): every rank that accumulates must hold the step sizes
+    acc = scores_out is not None and (shard is None or owner is None) and scores_from_cg(be, K)
+    tk = None
+    if acc:
+        scores_out.zero_()
+        tk = torch.empty_like(scores_out)              # K v of the current direction, this rank's rows
     t = be.zeros(M)
     v = be.zeros(M)
 
-    def mmv(s, out):
-        """out = A^-T [ T^-T K'K (T^-1 A^-1 s) / n + lam A^-1 s ]  (owner); every rank passes over K."""
+    def mmv(s, out, rows=None):
+        """out = A^-T [ T^-T K'K (T^-1 A^-1 s) / n + lam A^-1 s ]  (owner); every rank passes over K.
+        rows: receives K (T^-1 A^-1 s) for this rank's rows."""
         if owned:
             be.trmv(P, "LAit", s, out=v)               # A^-1 s
             be.trmv(P, "LTit", v, out=t)               # T^-1 A^-1 s
         bcast(t)
-        cc = ktk(v=t)                                  # K' K t, summed over shards
+        cc = ktk(v=t) if rows is None else ktk(v=t, t_out=rows)      # K' K t, summed over shards
         if owned:
             u = be.trmv(P, "LTi", cc, alpha=1.0 / n, beta=lam, z=v)   # T^-T cc / n + lam v
             be.trmv(P, "LAi", u, out=out)              # A^-T u
@@ -160,8 +186,8 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     cc2 = be.zeros(2 * ((M + 1) // 2 * 2)).view(2, -1) if can_fold else None     # (rows 16-byte aligned for odd M too)
     v2 = be.zeros(M) if can_fold else None
 
-    def mmv2(s1, out1, s2, out2):
-        """out1 = W s1 and out2 = W s2 from one read of K."""
+    def mmv2(s1, out1, s2, out2, rows=None):
+        """out1 = W s1 and out2 = W s2 from one read of K.  rows: receives K (T^-1 A^-1 s1) for this rank's rows."""
         t1, t2 = tt2[0, :M], tt2[1, :M]
         if owned:
             be.trmv(P, "LAit", s1, out=v)
@@ -170,7 +196,10 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
             be.trmv(P, "LTit", v2, out=t2)
         bcast(tt2)
         with ph("ktk2"):
-            be.ktk2(K, t1, t2, out1=cc2[0, :M], out2=cc2[1, :M])
+            if rows is None:
+                be.ktk2(K, t1, t2, out1=cc2[0, :M], out2=cc2[1, :M])
+            else:
+                be.ktk2(K, t1, t2, out1=cc2[0, :M], out2=cc2[1, :M], t_out=rows)
         ar(cc2)
         if owned:
             u = be.trmv(P, "LTi", cc2[0, :M], alpha=1.0 / n, beta=lam, z=v)
@@ -179,7 +208,7 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
             be.trmv(P, "LAi", u, out=out2)
 
     b0 = ar(b0)                                        # K' (y / n), summed over shards
-    one_call = shard is None and allreduce is None and phase is None and hasattr(be, "cg_solve")
+    one_call = shard is None and allreduce is None and phase is None and hasattr(be, "cg_solve") and not acc
     if one_call and getattr(K, "fmt", "f32") != "f32":
         # compact-format block: the class-batched library loop with a batch of one (odx_falkon_cg_batched_q_f64), where the
         # block's pass configuration has one and the factors are one contiguous block
@@ -216,11 +245,15 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
         full = (it + 1) % opt.cg_full_gradient_every == 0
         fold = can_fold and full and it != maxiter - 1
         if fold:
-            mmv2(Pv, AP, X, AX)                        # W p and W x_old
+            mmv2(Pv, AP, X, AX, rows=tk)               # W p and W x_old
         else:
-            mmv(Pv, AP)
+            mmv(Pv, AP, rows=tk)
         if owned:
             be.cg_step(X, R, Pv, AP, state, opt.cg_epsilon, full)
+        if acc:
+            # behind the step (state[3] is its size), in front of cg_finish: a flag raised by THIS iteration's cg_finish must
+            # not drop the term of the step X has just received; a flag raised earlier drops it as cg_step dropped the step
+            be.cg_scores_axpy(state, tk, scores_out)
         if it == maxiter - 1:
             break    # the residual / direction update of the last step cannot change the returned X
         if full and fold:
@@ -357,7 +390,7 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
 
 
 def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_total=None, shard=None, knm_outs=None,
-                        phase=None, precond=None, precond_ready=None, owners=None, knm_blocks=None):
+                        phase=None, precond=None, precond_ready=None, owners=None, knm_blocks=None, scores_out=None):
     """Fit up to `world` binary problems at once over row shards, one owner rank per problem.
 
     Problem b (labels ys[b], centres Zfs[b]) is owned by rank owners[b] (default: rank b): only that rank holds its
@@ -374,6 +407,10 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
     knm_outs    optional list of B preallocated f32 buffers for the K_nM shards
     knm_blocks  optional list that receives the B K_nM shards built here, in problem order
     precond     this rank's problem's preconditioner (when it owns one), or None to build it here
+    scores_out  optional list of B (n_local,) f64 device vectors: with ONE rank (which then holds every CG state) and blocks
+                for which scores_from_cg holds, vector b is zeroed and receives K_b alpha_b, summed step by step from the
+                passes' row products (see falkon_fit).  With more ranks the step sizes live on the owner only and the
+                vectors are left untouched: the caller scores from the stored block (backend.knm_mv)
     returns     list of B alpha vectors (M,) f64, on every rank
     """
     from .dist import RowShard
@@ -408,19 +445,30 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         knm_blocks.extend(Ks)
     tbuf, ccbuf, v = be.zeros(Mp), be.zeros(Mp), be.zeros(M)
     t, cc = tbuf[:M], ccbuf[:M]
+    # scores as a by-product of the passes (scores_from_cg): only where this rank holds the step sizes of every problem
+    acc = (scores_out is not None and world == 1 and B > 0 and len(scores_out) == B
+           and all(scores_from_cg(be, K) for K in Ks))
+    tks = None
+    if acc:
+        for S in scores_out:
+            S.zero_()
+        tks = [torch.empty_like(S) for S in scores_out]      # K v of problem b's current direction, this rank's rows
 
-    def passes():
+    def passes(rows=None):
         for b in range(B):
             with ph("ktk"):
-                be.ktk(Ks[b], v=Tall[owners[b], :M], out=CC[owners[b], :M])
+                if rows is None:
+                    be.ktk(Ks[b], v=Tall[owners[b], :M], out=CC[owners[b], :M])
+                else:
+                    be.ktk(Ks[b], v=Tall[owners[b], :M], out=CC[owners[b], :M], t_out=rows[b])
         return shard.reduce_scatter_rows(CC, ccbuf)
 
-    def mmv(s, out):
+    def mmv(s, out, rows=None):
         if owned:
             be.trmv(P, "LAit", s, out=v)
             be.trmv(P, "LTit", v, out=t)
         shard.gather_rows(tbuf, Tall)
-        passes()
+        passes(rows)
         if owned:
             u = be.trmv(P, "LTi", cc, alpha=1.0 / n, beta=lam, z=v)
             be.trmv(P, "LAi", u, out=out)
@@ -433,7 +481,7 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         Tall2 = be.zeros(world * 2 * Mp).view(world, 2 * Mp)
         CC2 = be.zeros(world * 2 * Mp).view(world, 2 * Mp)
 
-    def mmv2(s1, out1, s2, out2):
+    def mmv2(s1, out1, s2, out2, rows=None):
         if owned:
             be.trmv(P, "LAit", s1, out=v)
             be.trmv(P, "LTit", v, out=tbuf2[:M])
@@ -443,7 +491,10 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         for b in range(B):
             with ph("ktk2"):
                 o = owners[b]
-                be.ktk2(Ks[b], Tall2[o, :M], Tall2[o, Mp:Mp + M], out1=CC2[o, :M], out2=CC2[o, Mp:Mp + M])
+                if rows is None:
+                    be.ktk2(Ks[b], Tall2[o, :M], Tall2[o, Mp:Mp + M], out1=CC2[o, :M], out2=CC2[o, Mp:Mp + M])
+                else:
+                    be.ktk2(Ks[b], Tall2[o, :M], Tall2[o, Mp:Mp + M], out1=CC2[o, :M], out2=CC2[o, Mp:Mp + M], t_out=rows[b])
         shard.reduce_scatter_rows(CC2, ccbuf2)
         if owned:
             u = be.trmv(P, "LTi", ccbuf2[:M], alpha=1.0 / n, beta=lam, z=v)
@@ -465,11 +516,13 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         full = (it + 1) % opt.cg_full_gradient_every == 0
         fold = can_fold and full and it != maxiter - 1
         if fold:
-            mmv2(Pv, AP, X, AX)
+            mmv2(Pv, AP, X, AX, rows=tks)
         else:
-            mmv(Pv, AP)
+            mmv(Pv, AP, rows=tks)
         if owned:
             be.cg_step(X, R, Pv, AP, state, opt.cg_epsilon, full)
+        if acc:
+            be.cg_scores_axpy(state, tks[0], scores_out[0])      # (one rank: B == 1, its state; see falkon_fit for the place)
         if it == maxiter - 1:
             break
         if full and fold:
