@@ -11,6 +11,7 @@ Every array op is a libodx kernel reached through the backend; this file only se
 them and places the (optional) row-shard all-reduce.  No host synchronisation inside the loop:
 step sizes, residual norms and the stop flag stay on the device.
 """
+import math
 from dataclasses import dataclass
 
 import torch
@@ -89,6 +90,124 @@ def scores_from_cg(be, K):
                 and getattr(K, "fmt", None) in ("u24", "f32"))
 
 
+@dataclass
+class _CG:
+    """One conjugate-gradient state on the rank that holds it: the operator's pieces (preconditioner P, penalty lam), falkon's
+    vectors (right-hand side B, iterate X, residual R, direction Pv, W p in AP, W x in AX where the fold is on), the device
+    words `state`, and the state's places in its driver's exchange (see _slots)."""
+    P: object
+    lam: float
+    B: torch.Tensor
+    X: torch.Tensor
+    R: torch.Tensor
+    Pv: torch.Tensor
+    AP: torch.Tensor
+    AX: torch.Tensor            # None without the fold
+    state: torch.Tensor         # (4,): ||r||^2 old and new, the stop flag, the step size
+    v: tuple                    # scratch: A^-1 s of the first and of the second vector of a sandwich
+    io: list                    # io[k - 1][j] = (where T^-1 A^-1 s goes, where the summed K'K of it is read): vector j of k
+    alpha: torch.Tensor = None  # receives T^-1 A^-1 X (None: a new vector); set by _cg_run either way
+    tk: torch.Tensor = None     # with `scores`: K v of the current direction over this rank's rows (the passes' t_out)
+    scores: torch.Tensor = None
+
+
+def _slots(TT, CC, M, L=1, l=0):
+    """The io of state l of L over a driver's send / receive matrices ((L, Mp), or (2 L, Mp) where the fold is on): row l
+    carries the only vector of a one-vector exchange and the direction of a two-vector one, row L + l its iterate."""
+    return [[(TT[j * L + l, :M], CC[j * L + l, :M]) for j in range(k)] for k in range(1, TT.shape[0] // L + 1)]
+
+
+def _cg_state(be, P, lam, b0, M, io, fold, alpha=None, tk=None, scores=None):
+    """The CG state of (P, lam) at its start: B = A^-T T^-T b0 (b0 = K' (y / n), summed over shards), X = 0, R = Pv = B."""
+    X, R, Pv, AP = (be.zeros(M) for _ in range(4))
+    c = _CG(P, lam, be.trmv(P, "LAi", be.trmv(P, "LTi", b0)), X, R, Pv, AP, be.zeros(M) if fold else None, be.zeros(4),
+            (be.zeros(M), be.zeros(M) if fold else None), io, alpha, tk, scores)
+    be.cg_init(c.B, X, R, Pv, c.state)
+    return c
+
+
+def _pass(be, ph, K, T, C, M, t_out=None):
+    """C[j, :M] = K' (K T[j, :M]) for the one or two rows of T from one read of K.  t_out (receives K T[0, :M] over this
+    rank's rows) is passed on only when set: backends without score accumulation do not know the keyword."""
+    kw = {} if t_out is None else {"t_out": t_out}
+    if T.shape[0] == 2:
+        with ph("ktk2"):
+            be.ktk2(K, T[0, :M], T[1, :M], out1=C[0, :M], out2=C[1, :M], **kw)
+    else:
+        with ph("ktk"):
+            be.ktk(K, v=T[0, :M], out=C[0, :M], **kw)
+
+
+def _sum(ar, C):
+    """C summed over the row shards in place (an `allreduce` that returns another tensor is copied back)."""
+    r = ar(C)
+    if r is not C:
+        C.copy_(r)
+
+
+def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold):
+    """falkon's preconditioned CG schedule, for the states `cgs` this rank holds (none on a rank that only passes over its
+    rows), all advancing in lock step.  Returns with every c.alpha = T^-1 A^-1 x.
+
+    exchange(k, rows) is the driver's way through K'K: called once every state's k (1 or 2) prepared vectors T^-1 A^-1 s lie
+    in c.io[k - 1][j][0], it leaves the products, summed over the row shards, in c.io[k - 1][j][1] — by whatever collectives
+    and passes the driver uses, issued by every rank alike.  rows: the passes also write the row products K v of each state's
+    first vector to its tk.  can_fold is the driver's decision, identical on every rank, to take the periodic full residual
+    R = B - W x (falkon: every cg_full_gradient_every-th step) without a pass of its own: W is linear and
+    x_new = x_old + a p, so W x_new = W x_old + a W p, and W x_old comes out of the SAME read of K_nM as this step's W p (a
+    two-vector exchange).  Same value up to f64 rounding, and still computed from fresh products, so it keeps removing the
+    recursive drift the recomputation exists for.  No host synchronisation: step sizes and stop flags stay on the device."""
+    acc = any(c.scores is not None for c in cgs)
+
+    def W(*pairs, rows=False):
+        """c.<out> = W c.<s> for every (s, out) of pairs and every state c, W = A^-T [ T^-T K'K (T^-1 A^-1 .) / n + lam A^-1 . ],
+        from one exchange.  Vector kind outer, state inner."""
+        k = len(pairs)
+        for j, (s, _) in enumerate(pairs):
+            for c in cgs:
+                be.trmv(c.P, "LAit", getattr(c, s), out=c.v[j])        # A^-1 s
+                be.trmv(c.P, "LTit", c.v[j], out=c.io[k - 1][j][0])    # T^-1 A^-1 s
+        exchange(k, rows)                                              # K' K of each, summed over shards
+        for j, (_, out) in enumerate(pairs):
+            for c in cgs:
+                u = be.trmv(c.P, "LTi", c.io[k - 1][j][1], alpha=1.0 / n, beta=c.lam, z=c.v[j])    # T^-T cc / n + lam v
+                be.trmv(c.P, "LAi", u, out=getattr(c, out))            # A^-T u
+
+    tol = opt.cg_tolerance ** 2
+    for it in range(maxiter):
+        full = (it + 1) % opt.cg_full_gradient_every == 0
+        fold = can_fold and full and it != maxiter - 1
+        if fold:
+            W(("Pv", "AP"), ("X", "AX"), rows=acc)                     # W p and W x_old
+        else:
+            W(("Pv", "AP"), rows=acc)
+        for c in cgs:
+            be.cg_step(c.X, c.R, c.Pv, c.AP, c.state, opt.cg_epsilon, full)
+        for c in cgs:
+            if c.scores is not None:
+                # K alpha = sum_i a_i K v_i (scores_from_cg).  Behind the step (state[3] is its size), in front of cg_finish:
+                # a flag raised by THIS iteration's cg_finish must not drop the term of the step X has just received; a flag
+                # raised earlier drops it as cg_step dropped the step
+                be.cg_scores_axpy(c.state, c.tk, c.scores)
+        if it == maxiter - 1:
+            break    # the residual / direction update of the last step cannot change the returned X
+        if fold:
+            for c in cgs:
+                be.cg_residual(c.B, c.AX, c.AP, c.state, c.R)          # R = B - (W x_old + a W p) = B - W x_new
+        elif full:
+            W(("X", "AP"))
+            for c in cgs:
+                c.R.copy_(c.B)
+                be.axpby(-1.0, c.AP, 1.0, c.R)                         # R = B - W x
+        for c in cgs:
+            be.cg_finish(c.R, c.Pv, c.state, opt.cg_epsilon, tol)
+    for c in cgs:
+        c.alpha = be.trmv(c.P, "LTit", be.trmv(c.P, "LAit", c.X), out=c.alpha)    # T^-1 A^-1 beta
+    if opt.check_pivots:
+        for c in cgs:
+            _check_pivots(be, c.P)
+
+
 def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, allreduce=None, knm_out=None,
                return_knm=False, phase=None, precond=None, shard=None, owner=None, precond_ready=None, knm_blocks=None,
                scores_out=None):
@@ -146,66 +265,18 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
         K, b0 = be.knm_rhs(F, Zf, sigma, yn, out=knm_out)   # K_nM and this shard's K' (y / n), out of the same launch
     if knm_blocks is not None:
         knm_blocks.append(K)
-
-    def ktk(**kw):
-        with ph("ktk"):
-            r = be.ktk(K, **kw)
-        return ar(r)
-
     # scores as a by-product (see scores_from_cg): every rank that accumulates must hold the step sizes
     acc = scores_out is not None and (shard is None or owner is None) and scores_from_cg(be, K)
     tk = None
     if acc:
         scores_out.zero_()
         tk = torch.empty_like(scores_out)              # K v of the current direction, this rank's rows
-    t = be.zeros(M)
-    v = be.zeros(M)
-
-    def mmv(s, out, rows=None):
-        """out = A^-T [ T^-T K'K (T^-1 A^-1 s) / n + lam A^-1 s ]  (owner); every rank passes over K.
-        rows: receives K (T^-1 A^-1 s) for this rank's rows."""
-        if owned:
-            be.trmv(P, "LAit", s, out=v)               # A^-1 s
-            be.trmv(P, "LTit", v, out=t)               # T^-1 A^-1 s
-        bcast(t)
-        cc = ktk(v=t) if rows is None else ktk(v=t, t_out=rows)      # K' K t, summed over shards
-        if owned:
-            u = be.trmv(P, "LTi", cc, alpha=1.0 / n, beta=lam, z=v)   # T^-T cc / n + lam v
-            be.trmv(P, "LAi", u, out=out)              # A^-T u
-
-    # The periodic full residual R = B - W x (falkon: every cg_full_gradient_every-th step) without a pass of its own:
-    # W is linear and x_new = x_old + a p, so W x_new = W x_old + a W p, and W x_old comes out of the SAME read of K_nM
-    # as this step's W p (a two-vector pass, backend.ktk2).  Same value up to f64 rounding, and still computed from fresh
-    # products, so it keeps removing the recursive drift the recomputation exists for.  Used where the pass dominates
-    # the second vector's four extra triangular products (wide, tall blocks); otherwise the plain sequence below.
+    # the periodic full residual folded into the step's pass (see _cg_run): where the pass dominates the second vector's
+    # four extra triangular products (wide, tall blocks)
     if shard is not None:
         can_fold = _can_fold(be, K, M, int(n) // shard.world)
     else:
         can_fold = allreduce is None and _can_fold(be, K, M, int(n))
-    tt2 = be.zeros(2 * ((M + 1) // 2 * 2)).view(2, -1) if can_fold else None
-    cc2 = be.zeros(2 * ((M + 1) // 2 * 2)).view(2, -1) if can_fold else None     # (rows 16-byte aligned for odd M too)
-    v2 = be.zeros(M) if can_fold else None
-
-    def mmv2(s1, out1, s2, out2, rows=None):
-        """out1 = W s1 and out2 = W s2 from one read of K.  rows: receives K (T^-1 A^-1 s1) for this rank's rows."""
-        t1, t2 = tt2[0, :M], tt2[1, :M]
-        if owned:
-            be.trmv(P, "LAit", s1, out=v)
-            be.trmv(P, "LTit", v, out=t1)
-            be.trmv(P, "LAit", s2, out=v2)
-            be.trmv(P, "LTit", v2, out=t2)
-        bcast(tt2)
-        with ph("ktk2"):
-            if rows is None:
-                be.ktk2(K, t1, t2, out1=cc2[0, :M], out2=cc2[1, :M])
-            else:
-                be.ktk2(K, t1, t2, out1=cc2[0, :M], out2=cc2[1, :M], t_out=rows)
-        ar(cc2)
-        if owned:
-            u = be.trmv(P, "LTi", cc2[0, :M], alpha=1.0 / n, beta=lam, z=v)
-            be.trmv(P, "LAi", u, out=out1)
-            u = be.trmv(P, "LTi", cc2[1, :M], alpha=1.0 / n, beta=lam, z=v2)
-            be.trmv(P, "LAi", u, out=out2)
 
     b0 = ar(b0)                                        # K' (y / n), summed over shards
     one_call = shard is None and allreduce is None and phase is None and hasattr(be, "cg_solve") and not acc
@@ -215,10 +286,10 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
         one_call = bool(hasattr(be, "cg_batched_supported") and getattr(P, "block_rows", None) is not None
                         and be.cg_batched_supported([K.n], [K.M], K.fmt))
     if one_call:
-        # one shard, nothing to time per kernel family: the loop below as one library call (odx_falkon_cg_f64)
+        # one shard, nothing to time per kernel family: the schedule of _cg_run as one library call (odx_falkon_cg_f64)
         if precond_ready is not None:
             precond_ready()
-            precond_ready = None           # (waited for: the statement-by-statement loop below must not wait again)
+            precond_ready = None           # (waited for: the statement-by-statement schedule below must not wait again)
         if K.fmt != "f32":
             b0s = be.zeros((M + 1) // 2 * 2).view(1, -1)
             b0s[0, :M].copy_(b0)
@@ -229,52 +300,26 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     if one_call and alpha is not None:
         if opt.check_pivots:
             _check_pivots(be, P)
-        if return_knm:
-            return alpha, K
-        return alpha
-    X, R, Pv, AP = be.zeros(M), be.zeros(M), be.zeros(M), be.zeros(M)
-    AX = be.zeros(M) if can_fold else None
-    state = be.zeros(4)
+        return (alpha, K) if return_knm else alpha
+
+    k, Mp = 2 if can_fold else 1, (M + 1) // 2 * 2     # (rows 16-byte aligned for odd M too)
+    TT, CC = be.zeros(k * Mp).view(k, Mp), be.zeros(k * Mp).view(k, Mp)
+
+    def exchange(k, rows):
+        """The owner's vector(s) to every rank, every rank's pass over its rows, the partials summed."""
+        bcast(TT if k == 2 else TT[0, :M])
+        _pass(be, ph, K, TT[:k], CC[:k], M, tk if rows else None)
+        _sum(ar, CC if k == 2 else CC[0, :M])
+
+    alpha = be.zeros(M)
+    cgs = []
     if owned:
         if precond_ready is not None:
             precond_ready()
-        B = be.trmv(P, "LAi", be.trmv(P, "LTi", b0))   # A^-T T^-T b0
-        be.cg_init(B, X, R, Pv, state)
-    tol = opt.cg_tolerance ** 2
-    for it in range(maxiter):
-        full = (it + 1) % opt.cg_full_gradient_every == 0
-        fold = can_fold and full and it != maxiter - 1
-        if fold:
-            mmv2(Pv, AP, X, AX, rows=tk)               # W p and W x_old
-        else:
-            mmv(Pv, AP, rows=tk)
-        if owned:
-            be.cg_step(X, R, Pv, AP, state, opt.cg_epsilon, full)
-        if acc:
-            # behind the step (state[3] is its size), in front of cg_finish: a flag raised by THIS iteration's cg_finish must
-            # not drop the term of the step X has just received; a flag raised earlier drops it as cg_step dropped the step
-            be.cg_scores_axpy(state, tk, scores_out)
-        if it == maxiter - 1:
-            break    # the residual / direction update of the last step cannot change the returned X
-        if full and fold:
-            if owned:
-                be.cg_residual(B, AX, AP, state, R)    # R = B - (W x_old + a W p) = B - W x_new
-        elif full:
-            mmv(X, AP)
-            if owned:
-                R.copy_(B)
-                be.axpby(-1.0, AP, 1.0, R)             # R = B - mmv(X)
-        if owned:
-            be.cg_finish(R, Pv, state, opt.cg_epsilon, tol)
-    alpha = be.zeros(M)
-    if owned:
-        be.trmv(P, "LTit", be.trmv(P, "LAit", X), out=alpha)   # T^-1 A^-1 beta
-        if opt.check_pivots:
-            _check_pivots(be, P)
+        cgs.append(_cg_state(be, P, lam, b0, M, _slots(TT, CC, M), can_fold, alpha, tk, scores_out if acc else None))
+    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold)
     bcast(alpha)
-    if return_knm:
-        return alpha, K
-    return alpha
+    return (alpha, K) if return_knm else alpha
 
 
 def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=None, allreduce=None, phase=None, knm_out=None,
@@ -295,7 +340,6 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
     One shard, or replicated row shards through `allreduce` (in-place sum of an f64 device tensor: the (M,) right-hand
     side once, the (L, Mp) matrix of partial products once per pass; (2 L, Mp) at a folded iteration).  A backend without ktkn / precond_path is served
     by looping ktk / precond.  Other arguments as falkon_fit.  Returns the alphas, (L, M) f64."""
-    import math
     opt = opt or SolverOptions()
     lams = [float(x) for x in lams]
     if not lams or any(not (math.isfinite(x) and x > 0.0) for x in lams):
@@ -322,70 +366,25 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
     can_fold = bool(getattr(K, "fmt", None) == "stream" and hasattr(be, "ktkn") and hasattr(be, "ktkn_span")
                     and hasattr(be, "cg_residual") and 2 * L <= be.ktkn_span(K))
     rows = 2 * L if can_fold else L
-    TT2 = be.zeros(rows * Mp).view(rows, Mp)             # row l: T^-1 A_l^-1 s_l, the vector member l sends through K'K
-    CC2 = be.zeros(rows * Mp).view(rows, Mp)             # row l: K'K of it   (rows L .. 2 L - 1: the iterates of a folded step)
-    TT, CC = TT2[:L], CC2[:L]
-    vs = [be.zeros(M) for _ in range(rows)]
+    TT = be.zeros(rows * Mp).view(rows, Mp)              # row l: T^-1 A_l^-1 s_l, the vector member l sends through K'K
+    CC = be.zeros(rows * Mp).view(rows, Mp)              # row l: K'K of it   (rows L .. 2 L - 1: the iterates of a folded step)
 
-    def mmv_rows(S, out, TTr, CCr):
-        """out[l] = W_m S[l] for the rows of S (member m = l mod L), W_m = A_m^-T [ T^-T K'K (T^-1 A_m^-1 .) / n + lam_m A_m^-1 . ],
-        from one ktkn over K."""
-        for l in range(len(S)):
-            P = Ps[l % L]
-            be.trmv(P, "LAit", S[l], out=vs[l])
-            be.trmv(P, "LTit", vs[l], out=TTr[l, :M])
+    def exchange(k, rows):
+        """One ktkn over the k L rows in play, the partials summed."""
+        TTr, CCr = TT[:k * L], CC[:k * L]
         with ph("ktkn"):
             if hasattr(be, "ktkn"):
                 be.ktkn(K, TTr, out=CCr)
             else:
-                for l in range(len(S)):
+                for l in range(k * L):
                     be.ktk(K, v=TTr[l, :M], out=CCr[l, :M])
-        r = ar(CCr)
-        if r is not CCr:
-            CCr.copy_(r)
-        for l in range(len(S)):
-            P = Ps[l % L]
-            u = be.trmv(P, "LTi", CCr[l, :M], alpha=1.0 / n, beta=lams[l % L], z=vs[l])
-            be.trmv(P, "LAi", u, out=out[l])
+        _sum(ar, CCr)
 
-    def mmv_all(S, out):
-        mmv_rows(S, out, TT, CC)
-
-    X, R, Pv, AP = ([be.zeros(M) for _ in range(L)] for _ in range(4))
-    states = [be.zeros(4) for _ in range(L)]
-    Bs = []
-    for l, P in enumerate(Ps):
-        Bs.append(be.trmv(P, "LAi", be.trmv(P, "LTi", b0)))      # A_l^-T T^-T b0
-        be.cg_init(Bs[l], X[l], R[l], Pv[l], states[l])
-    tol = opt.cg_tolerance ** 2
-    AX = [be.zeros(M) for _ in range(L)] if can_fold else None
-    for it in range(maxiter):
-        full = (it + 1) % opt.cg_full_gradient_every == 0
-        fold = can_fold and full and it != maxiter - 1
-        if fold:
-            mmv_rows(Pv + X, AP + AX, TT2, CC2)          # W p and W x_old of every member from one build of K
-        else:
-            mmv_all(Pv, AP)
-        for l in range(L):
-            be.cg_step(X[l], R[l], Pv[l], AP[l], states[l], opt.cg_epsilon, full)
-        if it == maxiter - 1:
-            break    # the residual / direction update of the last step cannot change the returned X
-        if fold:
-            for l in range(L):
-                be.cg_residual(Bs[l], AX[l], AP[l], states[l], R[l])    # R = B - (W x_old + a W p) = B - W x_new
-        elif full:
-            mmv_all(X, AP)
-            for l in range(L):
-                R[l].copy_(Bs[l])
-                be.axpby(-1.0, AP[l], 1.0, R[l])         # R = B - W x
-        for l in range(L):
-            be.cg_finish(R[l], Pv[l], states[l], opt.cg_epsilon, tol)
+    cgs = [_cg_state(be, Ps[l], lams[l], b0, M, _slots(TT, CC, M, L, l), can_fold) for l in range(L)]
+    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold)
     alphas = be.zeros(L * M).view(L, M)
-    for l, P in enumerate(Ps):
-        alphas[l].copy_(be.trmv(P, "LTit", be.trmv(P, "LAit", X[l])))    # T^-1 A_l^-1 beta_l
-    if opt.check_pivots:
-        for P in Ps:
-            _check_pivots(be, P)
+    for l, c in enumerate(cgs):
+        alphas[l].copy_(c.alpha)
     return alphas
 
 
@@ -434,17 +433,16 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         with ph("precond"):
             P = be.precond(Zfs[owners.index(rank)], sigma, lam, opt.pc_epsilon)
     Mp = (M + 1) // 2 * 2                             # rows of the exchanged matrices stay 16-byte aligned
-    Tall = be.zeros(world * Mp).view(world, Mp)       # gathered directions: row r = the direction of the problem rank r owns
-    CC = be.zeros(world * Mp).view(world, Mp)         # this rank's partials: row r = its partial of the problem rank r owns
+    # Tall[k - 1] (world, k Mp): the gathered vectors, row r = the k vectors of the problem rank r owns; CC[k - 1]: this
+    # rank's partials, row r = its partials of that problem.  k = 2 (the fold): still one all-gather and one reduce-scatter
+    Tall, CC = ([be.zeros(world * Mp).view(world, Mp)] for _ in range(2))
     Ks = []
     for b in range(B):
         with ph("knm"):                               # K_nM shard and this shard's K' (y / n) of problem b in one launch
             Ks.append(be.knm_rhs(F, Zfs[b], sigma, ys[b] * (1.0 / n), out=None if knm_outs is None else knm_outs[b],
-                                 rhs_out=CC[owners[b], :M])[0])
+                                 rhs_out=CC[0][owners[b], :M])[0])
     if knm_blocks is not None:
         knm_blocks.extend(Ks)
-    tbuf, ccbuf, v = be.zeros(Mp), be.zeros(Mp), be.zeros(M)
-    t, cc = tbuf[:M], ccbuf[:M]
     # scores as a by-product of the passes (scores_from_cg): only where this rank holds the step sizes of every problem
     acc = (scores_out is not None and world == 1 and B > 0 and len(scores_out) == B
            and all(scores_from_cg(be, K) for K in Ks))
@@ -453,92 +451,31 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         for S in scores_out:
             S.zero_()
         tks = [torch.empty_like(S) for S in scores_out]      # K v of problem b's current direction, this rank's rows
-
-    def passes(rows=None):
-        for b in range(B):
-            with ph("ktk"):
-                if rows is None:
-                    be.ktk(Ks[b], v=Tall[owners[b], :M], out=CC[owners[b], :M])
-                else:
-                    be.ktk(Ks[b], v=Tall[owners[b], :M], out=CC[owners[b], :M], t_out=rows[b])
-        return shard.reduce_scatter_rows(CC, ccbuf)
-
-    def mmv(s, out, rows=None):
-        if owned:
-            be.trmv(P, "LAit", s, out=v)
-            be.trmv(P, "LTit", v, out=t)
-        shard.gather_rows(tbuf, Tall)
-        passes(rows)
-        if owned:
-            u = be.trmv(P, "LTi", cc, alpha=1.0 / n, beta=lam, z=v)
-            be.trmv(P, "LAi", u, out=out)
-
-    # the periodic full residual folded into the neighbouring step's pass (see falkon_fit): the exchanged matrices carry
-    # two vectors per problem for that one iteration — still one all-gather and one reduce-scatter
     can_fold = B > 0 and _can_fold(be, Ks[0], M, int(n) // world)
     if can_fold:
-        tbuf2, ccbuf2, v2 = be.zeros(2 * Mp), be.zeros(2 * Mp), be.zeros(M)
-        Tall2 = be.zeros(world * 2 * Mp).view(world, 2 * Mp)
-        CC2 = be.zeros(world * 2 * Mp).view(world, 2 * Mp)
+        Tall.append(be.zeros(world * 2 * Mp).view(world, 2 * Mp))
+        CC.append(be.zeros(world * 2 * Mp).view(world, 2 * Mp))
+    kmax = len(Tall)
+    mine, got = be.zeros(kmax * Mp).view(kmax, Mp), be.zeros(kmax * Mp).view(kmax, Mp)    # what this rank sends / is handed
 
-    def mmv2(s1, out1, s2, out2, rows=None):
-        if owned:
-            be.trmv(P, "LAit", s1, out=v)
-            be.trmv(P, "LTit", v, out=tbuf2[:M])
-            be.trmv(P, "LAit", s2, out=v2)
-            be.trmv(P, "LTit", v2, out=tbuf2[Mp:Mp + M])
-        shard.gather_rows(tbuf2, Tall2)
+    def exchange(k, rows):
+        """One all-gather of every owner's vector(s), B passes over this rank's rows, one reduce-scatter of the partials."""
+        Ta, Ca = Tall[k - 1], CC[k - 1]
+        shard.gather_rows(mine[:k].view(-1), Ta)
         for b in range(B):
-            with ph("ktk2"):
-                o = owners[b]
-                if rows is None:
-                    be.ktk2(Ks[b], Tall2[o, :M], Tall2[o, Mp:Mp + M], out1=CC2[o, :M], out2=CC2[o, Mp:Mp + M])
-                else:
-                    be.ktk2(Ks[b], Tall2[o, :M], Tall2[o, Mp:Mp + M], out1=CC2[o, :M], out2=CC2[o, Mp:Mp + M], t_out=rows[b])
-        shard.reduce_scatter_rows(CC2, ccbuf2)
-        if owned:
-            u = be.trmv(P, "LTi", ccbuf2[:M], alpha=1.0 / n, beta=lam, z=v)
-            be.trmv(P, "LAi", u, out=out1)
-            u = be.trmv(P, "LTi", ccbuf2[Mp:Mp + M], alpha=1.0 / n, beta=lam, z=v2)
-            be.trmv(P, "LAi", u, out=out2)
+            o = owners[b]
+            _pass(be, ph, Ks[b], Ta[o].view(k, Mp), Ca[o].view(k, Mp), M, tks[b] if rows else None)
+        shard.reduce_scatter_rows(Ca, got[:k].view(-1))
 
-    shard.reduce_scatter_rows(CC, ccbuf)             # K' (y / n) of every problem: each owner gets the sum of its row
-    X, R, Pv, AP, AX = be.zeros(M), be.zeros(M), be.zeros(M), be.zeros(M), be.zeros(M)
-    state = be.zeros(4)
-    Bv = None
+    shard.reduce_scatter_rows(CC[0], got[0])         # K' (y / n) of every problem: each owner gets the sum of its row
+    abuf = be.zeros(Mp)                              # this rank's problem's alpha (zeros on a rank that owns none)
+    cgs = []
     if owned:
         if precond_ready is not None:
             precond_ready()
-        Bv = be.trmv(P, "LAi", be.trmv(P, "LTi", cc))
-        be.cg_init(Bv, X, R, Pv, state)
-    tol = opt.cg_tolerance ** 2
-    for it in range(maxiter):
-        full = (it + 1) % opt.cg_full_gradient_every == 0
-        fold = can_fold and full and it != maxiter - 1
-        if fold:
-            mmv2(Pv, AP, X, AX, rows=tks)
-        else:
-            mmv(Pv, AP, rows=tks)
-        if owned:
-            be.cg_step(X, R, Pv, AP, state, opt.cg_epsilon, full)
-        if acc:
-            be.cg_scores_axpy(state, tks[0], scores_out[0])      # (one rank: B == 1, its state; see falkon_fit for the place)
-        if it == maxiter - 1:
-            break
-        if full and fold:
-            if owned:
-                be.cg_residual(Bv, AX, AP, state, R)
-        elif full:
-            mmv(X, AP)
-            if owned:
-                R.copy_(Bv)
-                be.axpby(-1.0, AP, 1.0, R)
-        if owned:
-            be.cg_finish(R, Pv, state, opt.cg_epsilon, tol)
-    tbuf.zero_()
-    if owned:
-        be.trmv(P, "LTit", be.trmv(P, "LAit", X), out=t)
-        if opt.check_pivots:
-            _check_pivots(be, P)
-    shard.gather_rows(tbuf, Tall)
-    return [Tall[owners[b], :M].clone() for b in range(B)]
+        b = owners.index(rank)
+        cgs.append(_cg_state(be, P, lam, got[0, :M], M, _slots(mine, got, M), can_fold, abuf[:M],
+                             tks[b] if acc else None, scores_out[b] if acc else None))
+    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold)
+    shard.gather_rows(abuf, Tall[0])
+    return [Tall[0][owners[b], :M].clone() for b in range(B)]
