@@ -248,6 +248,16 @@ int64_t odx_knm_fwd_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv
 int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
                        const double* V, int64_t ldv, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
                        odx_stream_t stream);
+/* out[q] = K' W[q], q = 0 .. nv - 1, 1 <= nv <= 8, from ONE read of a compact-format block: the right-hand sides K' (Y / n) of a
+ * multi-output fit (odx.solver.falkon_fit_multi), which odx_knm_fwd_bwd_q(v = NULL, w = W[q]) gives one read of the block at a
+ * time.  W: nv f64 rows of n weights, ldw doubles apart; out: nv f64 rows of M, ldo apart; rows 16-byte aligned, ldw and ldo
+ * even.  fmt ODX_KNM_U24 or ODX_KNM_BF16 and every M <= 20440 (no vector lives in LDS: the block is tiled as column bands x
+ * row ranges); the workspace twin returns a negative value for any other (M, fmt, nv) and the call ODX_ERR_UNSUPPORTED.
+ * Slab per row range and vector, fixed-order reduction: bitwise reproducible, no atomics. */
+int64_t odx_knm_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv);
+int odx_knm_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
+                   const double* W, int64_t ldw, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
+                   odx_stream_t stream);
 /* out[r * ldo] = (float) sum_j K[r, j] alpha[j], r < n, over a stored block in any of the three formats (scores from the
  * block a fit streamed: one read of it instead of a second Gaussian contraction).  Accumulated in f64 in a fixed order
  * (bitwise reproducible); no workspace.  M <= 20476; ldk (and ldlo for ODX_KNM_U24) a multiple of 4, >= roundup(M, 4);
@@ -350,6 +360,13 @@ int odx_falkon_precond_batched_f64(const float* const* Z, const int64_t* ldz, co
  * y = alpha * Tri x + beta * z  (z may be NULL when beta == 0; y may alias z).          */
 int odx_trmv_f64(const double* Tri, int64_t ld, int64_t M, int uplo, const double* x,
                  double alpha, double beta, const double* z, double* y, odx_stream_t stream);
+
+/* Y[q] = alpha * Tri X[q] + beta * Z[q] for q < nv, 1 <= nv <= 8, from ONE read of the factor (the states of a multi-output
+ * fit share one preconditioner).  X / Z / Y: nv f64 rows, ldx / ldz / ldy doubles apart; X rows 16-byte aligned, ldx even.
+ * Triangular ranges as odx_trmv_f64 (the other triangle is never read); Z may be NULL when beta == 0; Y may alias Z but not
+ * X.  Sums in a fixed order (not odx_trmv_f64's: the results agree to f64 rounding, not bit for bit). */
+int odx_trmvn_f64(const double* Tri, int64_t ld, int64_t M, int uplo, int nv, const double* X, int64_t ldx,
+                  double alpha, double beta, const double* Z, int64_t ldz, double* Y, int64_t ldy, odx_stream_t stream);
 
 /* ---------------------------------------------------------------- A4: CG vector updates
  * falkon ConjugateGradient.solve inner step for ONE right-hand side, all f64, length M,

@@ -503,6 +503,93 @@ __global__ __launch_bounds__(256) void trmv_f64_kernel(const double* __restrict_
   trmv_row(Tri, ld, M, uplo, x, alpha, beta, z, y);
 }
 
+// Y[q][i] = alpha * sum_{j in tri range} Tri[i][j] X[q][j] + beta * Z[q][i] for q < nv <= NV vectors from ONE read of the
+// factor (the T states of a multi-output fit share their preconditioner: solver.falkon_fit_multi).  A row-per-wave kernel that
+// re-read all NV vectors for every row would move NV times the factor's bytes through L2, so the rows are blocked: a wave
+// owns RB = 4 consecutive rows and uses every 16-byte fragment of X[q] it loads for all four (X traffic: NV / RB of the
+// factor's).  The fast loop runs over the aligned pairs common to the block's rows; what a row's range holds beyond them (the
+// diagonal corner, an odd end: at most RB + 1 elements at either side) is taken one element per lane, inside the row's range
+// only — the other triangle is never read.  The RB x NV sums of a wave are reduced transposing (knm_pass_nv.hip); every order
+// of additions is fixed.  Longest rows first, as trmv_row.  Vectors past nv repeat vector nv - 1 and are not stored.
+template <int NV>
+__global__ __launch_bounds__(256) void trmvn_f64_kernel(const double* __restrict__ Tri, int64_t ld, int64_t M, int uplo, int nv,
+                                                        const double* __restrict__ X, int64_t ldx, double alpha, double beta,
+                                                        const double* Z, int64_t ldz, double* Y, int64_t ldy) {
+  constexpr int RB = 4, N = RB * NV;
+  static_assert((N & (N - 1)) == 0 && N <= 64, "the transposing reduction needs a power-of-two count of sums");
+  const int lane = threadIdx.x & 63;
+  const int64_t nrb = (M + RB - 1) / RB;
+  int64_t rb = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (rb >= nrb) return;
+  if (!uplo) rb = nrb - 1 - rb;
+  const int64_t i0 = rb * RB, i1 = i0 + RB < M ? i0 + RB : M;      // the block's rows [i0, i1)
+  // pairs [2 q0, 2 q1) lie inside the range of every row of the block
+  const int64_t q0 = uplo ? i1 >> 1 : 0, q1 = uplo ? M >> 1 : (i0 + 1) >> 1;      // (upper: ceil((i1 - 1) / 2))
+  const double* row[RB];
+  const double* xq[NV];
+#pragma unroll
+  for (int k = 0; k < RB; ++k) row[k] = Tri + (i0 + k < M ? i0 + k : M - 1) * ld;
+#pragma unroll
+  for (int q = 0; q < NV; ++q) xq[q] = X + (int64_t)(q < nv ? q : nv - 1) * ldx;
+  double acc[RB][NV];
+#pragma unroll
+  for (int k = 0; k < RB; ++k)
+#pragma unroll
+    for (int q = 0; q < NV; ++q) acc[k][q] = 0.0;
+  // the elements of a row's range outside the common pairs: lanes 0 .. 7 walk up from 2 q1, lanes 8 .. 15 down from 2 q0 - 1
+  if (lane < 16) {
+    const int64_t j = lane < 8 ? 2 * q1 + lane : 2 * q0 - 1 - (lane - 8);
+#pragma unroll
+    for (int k = 0; k < RB; ++k) {
+      const int64_t i = i0 + k;
+      const int64_t jlo = uplo ? i : 0, jhi = uplo ? M : i + 1;
+      if (i < M && j >= jlo && j < jhi) {
+        const double a = row[k][j];
+#pragma unroll
+        for (int q = 0; q < NV; ++q) acc[k][q] = a * xq[q][j];
+      }
+    }
+  }
+  for (int64_t p = q0 + lane; p < q1; p += 64) {
+    f64x2 a[RB];
+#pragma unroll
+    for (int k = 0; k < RB; ++k) a[k] = *reinterpret_cast<const f64x2*>(row[k] + 2 * p);
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+      const f64x2 b = *reinterpret_cast<const f64x2*>(xq[q] + 2 * p);
+#pragma unroll
+      for (int k = 0; k < RB; ++k) acc[k][q] = fma(a[k][1], b[1], fma(a[k][0], b[0], acc[k][q]));
+    }
+  }
+  // transposing reduction: at every step a lane hands half of its values to its partner and keeps the sums of the other
+  // half; lane l ends with the total of value idx(l)
+  double* s = &acc[0][0];
+  int off = 32;
+#pragma unroll
+  for (int half = N / 2; half >= 1; half >>= 1, off >>= 1) {
+    const bool up = (lane & off) != 0;
+#pragma unroll
+    for (int i = 0; i < half; ++i) {
+      const double give = up ? s[i] : s[half + i], keep = up ? s[half + i] : s[i];
+      s[i] = keep + __shfl_xor(give, off);
+    }
+  }
+#pragma unroll
+  for (; off > 0; off >>= 1) s[0] += __shfl_xor(s[0], off);
+  int idx = 0, bit = 32;
+#pragma unroll
+  for (int half = N / 2; half >= 1; half >>= 1, bit >>= 1) idx += (lane & bit) ? half : 0;
+  if ((lane & (64 / N - 1)) == 0 || N == 64) {
+    const int k = idx / NV, q = idx % NV;
+    const int64_t i = i0 + k;
+    if (i < M && q < nv) {
+      double r = alpha * s[0];
+      if (beta != 0.0) r += beta * Z[(int64_t)q * ldz + i];
+      Y[(int64_t)q * ldy + i] = r;
+    }
+  }
+}
+
 // The same product for the classes of a batch (blockIdx.y = class): factors tri_stride apart, vectors vstride apart,
 // each class with its own size and (when `scaled`) its own alpha.  Per class the arithmetic of trmv_f64_kernel.
 __global__ __launch_bounds__(256) void trmv_batched_kernel(const double* __restrict__ Tri, int64_t ld, int64_t tri_stride,
@@ -931,6 +1018,27 @@ extern "C" int odx_trmv_f64(const double* Tri, int64_t ld, int64_t M, int uplo, 
   hipLaunchKernelGGL(trmv_f64_kernel, dim3((unsigned)ceil_div(M, 4)), dim3(256), 0, as_stream(stream), Tri, ld, M,
                      uplo, x, alpha, beta, z, y);
   ODX_CHECK_LAUNCH("odx_trmv_f64");
+  return ODX_OK;
+}
+
+extern "C" int odx_trmvn_f64(const double* Tri, int64_t ld, int64_t M, int uplo, int nv, const double* X, int64_t ldx, double alpha,
+                             double beta, const double* Z, int64_t ldz, double* Y, int64_t ldy, odx_stream_t stream) {
+  ODX_REQUIRE(nv >= 1 && nv <= 8, "odx_trmvn_f64: 1 .. 8 vectors per call (got %d)", nv);
+  if (M <= 0) return ODX_OK;
+  ODX_REQUIRE(Tri && X && Y && (beta == 0.0 || Z), "odx_trmvn_f64: null pointer");
+  ODX_REQUIRE(ld % 2 == 0 && ld >= M && aligned16(Tri) && aligned16(X) && ldx % 2 == 0,
+              "odx_trmvn_f64: Tri/X must be 16-byte aligned, ld and ldx even, ld >= M");
+  ODX_REQUIRE(nv == 1 || (ldx >= M && ldy >= M && (beta == 0.0 || ldz >= M)), "odx_trmvn_f64: rows of X, Z and Y must be M apart or more");
+  ODX_REQUIRE(X != Y, "odx_trmvn_f64: X and Y must not alias");
+  const dim3 grid((unsigned)ceil_div(ceil_div(M, (int64_t)4), (int64_t)4));      // four row blocks of four rows per workgroup
+#define ODX_TRMVN(NV_)                                                                                                            \
+  hipLaunchKernelGGL(trmvn_f64_kernel<NV_>, grid, dim3(256), 0, as_stream(stream), Tri, ld, M, uplo, nv, X, ldx, alpha, beta, Z, ldz, \
+                     Y, ldy)
+  if (nv <= 2) ODX_TRMVN(2);
+  else if (nv <= 4) ODX_TRMVN(4);
+  else ODX_TRMVN(8);
+#undef ODX_TRMVN
+  ODX_CHECK_LAUNCH("odx_trmvn_f64");
   return ODX_OK;
 }
 

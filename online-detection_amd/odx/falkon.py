@@ -20,7 +20,7 @@ import torch
 
 from . import backend as _backend
 from . import options as _options
-from .solver import SolverOptions, falkon_fit, falkon_fit_path
+from .solver import SolverOptions, falkon_fit, falkon_fit_multi, falkon_fit_path
 
 
 class FalkonOptions:
@@ -101,6 +101,16 @@ class _FalkonBase:
         self.ny_points_ = None
 
     def fit(self, X, Y, Xts=None, Yts=None):
+        return self._fit(X, Y, multi=False)
+
+    def fit_multi(self, X, Y):
+        """Fit the T >= 1 columns of Y (n, T) as T outputs of ONE model over the same rows and centres, from one K_nM block
+        and one preconditioner (solver.falkon_fit_multi): `alpha_` becomes (M, T) and `predict` returns (n, T), as the upstream
+        estimator's fit does for a label matrix.  Centres, `ny_points_` and the centre cache are handled as by `fit`; one column
+        takes `fit`'s code path, bit for bit.  (`fit` itself keeps refusing more than one column.)"""
+        return self._fit(X, Y, multi=True)
+
+    def _fit(self, X, Y, multi):
         be = _backend.get_backend()
         F = be.features(X)
         if isinstance(self.center_selection, str):
@@ -112,16 +122,21 @@ class _FalkonBase:
             Zf = be.features(Z)
         self.M = Zf.n
         y = torch.as_tensor(Y).reshape(F.n, -1)
-        if y.shape[1] != 1:
+        if y.shape[1] != 1 and not (multi and y.shape[1] > 1):
             raise ValueError("odx FALKON fits one right-hand side per model (the reference trains one "
                              "binary classifier per fit); got Y with %d columns" % y.shape[1])
-        yv = be.vec(y[:, 0])
-        alpha = falkon_fit(be, F, yv, Zf, self.kernel.sigma, float(self.penalty), int(self.maxiter),
-                           self.options.solver_options())
+        if y.shape[1] == 1:
+            yv = be.vec(y[:, 0])
+            alpha = falkon_fit(be, F, yv, Zf, self.kernel.sigma, float(self.penalty), int(self.maxiter),
+                               self.options.solver_options()).reshape(-1, 1)
+        else:
+            # T label columns over the same rows and centres: one block, one preconditioner
+            alpha = falkon_fit_multi(be, F, be.vec(y), Zf, self.kernel.sigma, float(self.penalty), int(self.maxiter),
+                                     self.options.solver_options()).t().contiguous()          # (M, T), as upstream's alpha_
         if hasattr(be, "release_helper_streams"):
             be.release_helper_streams()          # (a chain of 4096 centres or more made helper streams: not left behind idle)
         ny = Zf.X.contiguous() if Zf.X.stride(0) != Zf.D else Zf.X
-        self.alpha_ = alpha.reshape(-1, 1)
+        self.alpha_ = alpha
         self.ny_points_ = ny
         if self._cpu_model:
             self.alpha_ = self.alpha_.cpu()

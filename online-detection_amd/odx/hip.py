@@ -90,6 +90,8 @@ SIGNATURES = {
     "odx_knm_fwd_bwd2_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_knm_fwd_bwdn_q_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "odx_knm_fwd_bwdn_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "odx_knm_bwdn_q_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "odx_knm_bwdn_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "odx_knm_mv": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _i64, _vp]),
     "odx_gauss_ktk_stream_h2_rows": (_i64, [_i64, _i32]),
     "odx_gauss_ktk_stream_h2_workspace_bytes": (_i64, [_i64, _i64, _i32]),
@@ -112,6 +114,7 @@ SIGNATURES = {
     "odx_falkon_precond_batched_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "odx_falkon_precond_batched_f64": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _f64, _f64, _f64, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "odx_trmv_f64": (_i32, [_vp, _i64, _i64, _i32, _vp, _f64, _f64, _vp, _vp, _vp]),
+    "odx_trmvn_f64": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i64, _f64, _f64, _vp, _i64, _vp, _i64, _vp]),
     "odx_cg_init": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_cg_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _f64, _i32, _i64, _vp]),
     "odx_cg_finish": (_i32, [_vp, _vp, _vp, _f64, _f64, _i64, _vp]),

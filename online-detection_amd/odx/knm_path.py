@@ -1,8 +1,12 @@
-"""Backend operations of a lambda path (solver.falkon_fit_path): L fits that share one K_nM block.
+"""Backend operations of fits that share one K_nM block: a lambda path (solver.falkon_fit_path: L penalties) and a
+multi-output fit (solver.falkon_fit_multi: T label columns, which share the preconditioner too).
 
 ``PathOps`` is mixed into ``backend.HipBackend``.  It adds the pass over several vectors from one read of the block
 (``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, the existing one- and two-vector passes for the rest; on a
-streamed shard odx_gauss_ktk_stream_h2n, up to 16 vectors from one BUILD of K) and the preconditioners of a lambda path (``precond_path``: odx_falkon_precond_path_f64), both HIP through libodx.
+streamed shard odx_gauss_ktk_stream_h2n, up to 16 vectors from one BUILD of K), the preconditioners of a lambda path
+(``precond_path``: odx_falkon_precond_path_f64), the right-hand sides of several label columns from one read of the block
+(``ktwn``: odx_knm_bwdn_q) and the triangular products of several vectors from one read of a factor (``trmvn``:
+odx_trmvn_f64), all HIP through libodx.
 """
 import ctypes
 
@@ -90,6 +94,57 @@ class PathOps:
             else:
                 for j in range(l, l + g):
                     self.ktk(K, v=V[j, :M], out=out[j, :M])
+        return out
+
+    def ktwn(self, K, W, out=None):
+        """out[t] = K' W[t] for the T >= 1 rows of W ((T, >= K.n) f64): the right-hand sides of T label columns.  A compact
+        stored block: groups of up to 8 rows from ONE read each (odx_knm_bwdn_q, every M the compact passes serve); a group
+        of one goes through ktk(K, w=...).  f32 blocks (small, not HBM-bound: ktkn's decision) loop ktk(K, w=...), and so do
+        streamed shards — there every row is one recompute of K: a build-once entry for several weight vectors is NOT
+        built.  Rows of W and out must be 16-byte aligned for groups of 2 or more."""
+        T, M, n = W.shape[0], K.M, K.n
+        if out is None:
+            out = torch.zeros((T, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
+        for t, cols in ((W, n), (out, M)):
+            if t.dim() != 2 or t.shape[0] != T or t.shape[1] < cols or t.dtype != torch.float64 or t.stride(1) != 1:
+                raise ValueError("ktwn: W must be a (T, >= n) and out a (T, >= M) f64 matrix with contiguous rows")
+        for l in range(0, T, 8 if K.fmt in _CODE else 1):
+            g = min(8, T - l) if K.fmt in _CODE else 1
+            if g == 1:
+                self.ktk(K, w=W[l, :n], out=out[l, :M])
+                continue
+            if W.stride(0) % 2 or out.stride(0) % 2 or W[l].data_ptr() % 16 or out[l].data_ptr() % 16:
+                raise ValueError("ktwn: rows of W and out must be 16-byte aligned (even leading dimension)")
+            nbytes = self.lib.odx_knm_bwdn_q_workspace_bytes(max(n, 1), M, _CODE[K.fmt], g)
+            if nbytes < 0:
+                raise hip.OdxError("odx_knm_bwdn_q: M = %d is outside the supported range (M <= 20440)" % M)
+            ws = self._workspace("ktk", nbytes)
+            hip.check(self.lib.odx_knm_bwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], n, M, g,
+                                              _p(W[l]), W.stride(0), _p(out[l]), out.stride(0), _p(ws), ws.numel(), self._stream()),
+                      "odx_knm_bwdn_q")
+        return out
+
+    def trmvn(self, P, name, X, alpha=1.0, beta=0.0, Z=None, out=None):
+        """out[t] = alpha * P.<name> X[t] + beta * Z[t] over the rows of (T, >= P.M) f64 matrices: groups of up to 8 rows from
+        ONE read of the factor each (odx_trmvn_f64); one row goes through trmv.  out may be Z, not X."""
+        T, M = X.shape[0], P.M
+        if out is None:
+            out = torch.zeros((T, P.ld), dtype=torch.float64, device=self.device)
+        for t in (X, out) + (() if Z is None else (Z,)):
+            if t.dim() != 2 or t.shape[0] != T or t.shape[1] < M or t.dtype != torch.float64 or t.stride(1) != 1:
+                raise ValueError("trmvn: X, Z and out must be (T, >= M) f64 matrices with contiguous rows")
+        if beta != 0.0 and Z is None:
+            raise ValueError("trmvn: beta needs Z")
+        for l in range(0, T, 8):
+            g = min(8, T - l)
+            if g == 1:
+                self.trmv(P, name, X[l], alpha=alpha, beta=beta, z=None if Z is None else Z[l], out=out[l])
+                continue
+            if X.stride(0) % 2 or X[l].data_ptr() % 16:
+                raise ValueError("trmvn: rows of X must be 16-byte aligned (even leading dimension)")
+            hip.check(self.lib.odx_trmvn_f64(_p(getattr(P, name)), P.ld, M, self._TRI[name], g, _p(X[l]), X.stride(0), float(alpha),
+                                             float(beta), None if Z is None else _p(Z[l]), 0 if Z is None else Z.stride(0), _p(out[l]),
+                                             out.stride(0), self._stream()), "odx_trmvn_f64")
         return out
 
     def precond_path(self, Zf, sigma, lams, eps, out=None, ws_key="precond"):

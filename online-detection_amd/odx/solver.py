@@ -111,6 +111,20 @@ class _CG:
     scores: torch.Tensor = None
 
 
+class _Rows:
+    """The vectors of L states that share ONE preconditioner and penalty (a multi-output fit) as the rows of (L, Mp) matrices,
+    with the driver's exchange matrices `send` / `recv` (_slots: state l sends row j L + l and reads it back): what lets
+    _cg_run send a triangular product of all L states through one be.trmvn (one read of the factor)."""
+
+    def __init__(self, be, L, Mp, fold, send, recv):
+        def mat():
+            return be.zeros(L * Mp).view(L, Mp)
+        self.B, self.X, self.R, self.Pv, self.AP, self.U, self.alpha = (mat() for _ in range(7))
+        self.AX = mat() if fold else None
+        self.v = (mat(), mat() if fold else None)
+        self.send, self.recv = send, recv
+
+
 def _slots(TT, CC, M, L=1, l=0):
     """The io of state l of L over a driver's send / receive matrices ((L, Mp), or (2 L, Mp) where the fold is on): row l
     carries the only vector of a one-vector exchange and the direction of a two-vector one, row L + l its iterate."""
@@ -145,7 +159,7 @@ def _sum(ar, C):
         C.copy_(r)
 
 
-def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold):
+def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared=None):
     """falkon's preconditioned CG schedule, for the states `cgs` this rank holds (none on a rank that only passes over its
     rows), all advancing in lock step.  Returns with every c.alpha = T^-1 A^-1 x.
 
@@ -156,10 +170,28 @@ def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold):
     R = B - W x (falkon: every cg_full_gradient_every-th step) without a pass of its own: W is linear and
     x_new = x_old + a p, so W x_new = W x_old + a W p, and W x_old comes out of the SAME read of K_nM as this step's W p (a
     two-vector exchange).  Same value up to f64 rounding, and still computed from fresh products, so it keeps removing the
-    recursive drift the recomputation exists for.  No host synchronisation: step sizes and stop flags stay on the device."""
-    acc = any(c.scores is not None for c in cgs)
+    recursive drift the recomputation exists for.  No host synchronisation: step sizes and stop flags stay on the device.
 
-    def W(*pairs, rows=False):
+    shared: the _Rows whose matrices the vectors of ALL states are rows of, state l row l — the driver's statement that they
+    share one P and lam and that the backend has trmvn: every triangular product of the L states is then one be.trmvn.
+    Without it _cg_run issues one be.trmv per state and product."""
+    acc = any(c.scores is not None for c in cgs)
+    sh = shared
+    if sh is not None:
+        P, lam, L = cgs[0].P, cgs[0].lam, len(cgs)
+
+    def Wn(*pairs, rows=False):
+        """W for states that share P: every triangular product of the L states from ONE read of its factor."""
+        k = len(pairs)
+        for j, (s, _) in enumerate(pairs):
+            be.trmvn(P, "LAit", getattr(sh, s), out=sh.v[j])                                   # A^-1 s
+            be.trmvn(P, "LTit", sh.v[j], out=sh.send[j * L:(j + 1) * L])                       # T^-1 A^-1 s
+        exchange(k, rows)
+        for j, (_, out) in enumerate(pairs):
+            be.trmvn(P, "LTi", sh.recv[j * L:(j + 1) * L], alpha=1.0 / n, beta=lam, Z=sh.v[j], out=sh.U)    # T^-T cc / n + lam v
+            be.trmvn(P, "LAi", sh.U, out=getattr(sh, out))                                     # A^-T u
+
+    def W1(*pairs, rows=False):
         """c.<out> = W c.<s> for every (s, out) of pairs and every state c, W = A^-T [ T^-T K'K (T^-1 A^-1 .) / n + lam A^-1 . ],
         from one exchange.  Vector kind outer, state inner."""
         k = len(pairs)
@@ -173,6 +205,7 @@ def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold):
                 u = be.trmv(c.P, "LTi", c.io[k - 1][j][1], alpha=1.0 / n, beta=c.lam, z=c.v[j])    # T^-T cc / n + lam v
                 be.trmv(c.P, "LAi", u, out=getattr(c, out))            # A^-T u
 
+    W = W1 if sh is None else Wn
     tol = opt.cg_tolerance ** 2
     for it in range(maxiter):
         full = (it + 1) % opt.cg_full_gradient_every == 0
@@ -201,10 +234,15 @@ def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold):
                 be.axpby(-1.0, c.AP, 1.0, c.R)                         # R = B - W x
         for c in cgs:
             be.cg_finish(c.R, c.Pv, c.state, opt.cg_epsilon, tol)
-    for c in cgs:
-        c.alpha = be.trmv(c.P, "LTit", be.trmv(c.P, "LAit", c.X), out=c.alpha)    # T^-1 A^-1 beta
-    if opt.check_pivots:
+    if sh is not None:
+        be.trmvn(P, "LTit", be.trmvn(P, "LAit", sh.X, out=sh.U), out=sh.alpha)    # T^-1 A^-1 beta
+        for l, c in enumerate(cgs):
+            c.alpha = sh.alpha[l, :P.M]
+    else:
         for c in cgs:
+            c.alpha = be.trmv(c.P, "LTit", be.trmv(c.P, "LAit", c.X), out=c.alpha)    # T^-1 A^-1 beta
+    if opt.check_pivots:
+        for c in (cgs[:1] if sh is not None else cgs):      # (one shared preconditioner: one status word)
             _check_pivots(be, c.P)
 
 
@@ -347,7 +385,6 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
     L = len(lams)
     n = float(F.n if n_total is None else n_total)
     M = Zf.n
-    Mp = (M + 1) // 2 * 2                                # rows of the shared matrices stay 16-byte aligned
     ar = allreduce if allreduce is not None else (lambda v: v)
     ph = phase if phase is not None else (lambda name: _NoPhase())
 
@@ -362,7 +399,16 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
         knm_blocks.append(K)
     b0 = ar(b0)                                          # K' (y / n), summed over shards
 
-    # the fold of the periodic full residual (see the docstring): streamed shards whose one build serves 2 L vectors
+    return _fit_members(be, K, [(P, lam, b0) for P, lam in zip(Ps, lams)], M, n, maxiter, opt, ar, ph)
+
+
+def _fit_members(be, K, members, M, n, maxiter, opt, ar, ph, B0=None):
+    """The L conjugate-gradient states (P, lam, b0) of `members` over ONE block K in lock step: the driver falkon_fit_path (one
+    P per lambda, one b0) and falkon_fit_multi (one P and lambda, one b0 per label column: B0, the (L, Mp) matrix the b0 are
+    rows of) share.  Returns the alphas, (L, M) f64."""
+    L = len(members)
+    Mp = (M + 1) // 2 * 2                                # rows of the shared matrices stay 16-byte aligned
+    # the fold of the periodic full residual (see falkon_fit_path): streamed shards whose one build serves 2 L vectors
     can_fold = bool(getattr(K, "fmt", None) == "stream" and hasattr(be, "ktkn") and hasattr(be, "ktkn_span")
                     and hasattr(be, "cg_residual") and 2 * L <= be.ktkn_span(K))
     rows = 2 * L if can_fold else L
@@ -380,12 +426,83 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
                     be.ktk(K, v=TTr[l, :M], out=CCr[l, :M])
         _sum(ar, CCr)
 
-    cgs = [_cg_state(be, Ps[l], lams[l], b0, M, _slots(TT, CC, M, L, l), can_fold) for l in range(L)]
-    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold)
+    shared = None
+    if B0 is not None:
+        # one preconditioner for all members: their vectors are the rows of common matrices (_Rows), and where the backend has
+        # trmvn every triangular product of all of them — B = A^-T T^-T b0 here, the rest in _cg_run — is one read of a factor
+        P, lam = members[0][0], members[0][1]
+        sh = _Rows(be, L, Mp, can_fold, TT, CC)
+        if L > 1 and hasattr(be, "trmvn"):
+            shared = sh
+            be.trmvn(P, "LAi", be.trmvn(P, "LTi", B0, out=sh.U), out=sh.B)
+        else:
+            for l in range(L):
+                sh.B[l, :M].copy_(be.trmv(P, "LAi", be.trmv(P, "LTi", B0[l, :M])))
+        cgs = []
+        for l in range(L):
+            c = _CG(P=P, lam=lam, B=sh.B[l, :M], X=sh.X[l, :M], R=sh.R[l, :M], Pv=sh.Pv[l, :M], AP=sh.AP[l, :M],
+                    AX=sh.AX[l, :M] if can_fold else None, state=be.zeros(4),
+                    v=(sh.v[0][l, :M], sh.v[1][l, :M] if can_fold else None), io=_slots(TT, CC, M, L, l))
+            be.cg_init(c.B, c.X, c.R, c.Pv, c.state)
+            cgs.append(c)
+    else:
+        cgs = [_cg_state(be, P, lam, b0, M, _slots(TT, CC, M, L, l), can_fold) for l, (P, lam, b0) in enumerate(members)]
+    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared)
     alphas = be.zeros(L * M).view(L, M)
     for l, c in enumerate(cgs):
         alphas[l].copy_(c.alpha)
     return alphas
+
+
+def falkon_fit_multi(be, F, Y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, allreduce=None, phase=None, knm_out=None,
+                     knm_blocks=None):
+    """Fit the T columns of a label matrix from ONE K_nM block and ONE preconditioner (one-vs-rest heads on shared rows and
+    centres: what T calls of falkon_fit build T times).
+
+    Y is (n_local, T) f64, a column per output (the layout of the upstream estimator's Y); the alphas come back as (T, M)
+    f64, row t for column t.  Nothing but the right-hand side and the CG vectors depends on the column: one be.precond, one
+    be.knm_rhs (column 0 keeps the build's fused right-hand side, so T = 1 is falkon_fit's statement-by-statement sequence,
+    operation for operation), the right-hand sides K' (Y[:, t] / n) of the other columns from one be.ktwn (phase "ktwn"; a
+    backend without it loops ktk(K, w=...)), and T conjugate-gradient states that all point at the same preconditioner,
+    each following falkon_fit's schedule with its own device-side stop flag: per iteration one be.ktkn over the T
+    directions, and every triangular product of all T states from one read of its factor (be.trmvn, where the backend
+    has it).  The periodic full residual as in falkon_fit_path: its plain form on stored blocks, folded into the step's
+    build where a streamed shard's ktkn_span holds 2 T.  No host synchronisation inside the loop.
+
+    One shard, or replicated row shards through `allreduce` (in-place sum of an f64 device tensor: the (M,) right-hand
+    side of column 0, the (T - 1, Mp) matrix of the others, then the matrix of partial products once per pass).  Other
+    arguments as falkon_fit."""
+    opt = opt or SolverOptions()
+    if Y.dim() != 2 or Y.shape[0] != F.n or Y.shape[1] < 1:
+        raise ValueError("falkon_fit_multi: Y must be (n_local, T) with the %d rows of F, got %r" % (F.n, tuple(Y.shape)))
+    T = Y.shape[1]
+    n = float(F.n if n_total is None else n_total)
+    M = Zf.n
+    Mp = (M + 1) // 2 * 2
+    ar = allreduce if allreduce is not None else (lambda v: v)
+    ph = phase if phase is not None else (lambda name: _NoPhase())
+
+    with ph("precond"):
+        P = be.precond(Zf, sigma, lam, opt.pc_epsilon)
+    with ph("knm"):
+        K, b0 = be.knm_rhs(F, Zf, sigma, Y[:, 0] * (1.0 / n), out=knm_out)
+    if knm_blocks is not None:
+        knm_blocks.append(K)
+    B0 = be.zeros(T * Mp).view(T, Mp)                    # row t: K' (Y[:, t] / n), summed over shards
+    B0[0, :M].copy_(ar(b0))
+    if T > 1:
+        nl = F.n
+        Wn = be.zeros((T - 1) * ((nl + 1) // 2 * 2)).view(T - 1, -1)      # (rows 16-byte aligned for odd n too)
+        Wn[:, :nl].copy_(Y[:, 1:].t())
+        Wn.mul_(1.0 / n)
+        with ph("ktwn"):
+            if hasattr(be, "ktwn"):
+                be.ktwn(K, Wn, out=B0[1:])
+            else:
+                for t in range(T - 1):
+                    be.ktk(K, w=Wn[t, :nl], out=B0[t + 1, :M])
+        _sum(ar, B0[1:])
+    return _fit_members(be, K, [(P, float(lam), B0[t, :M]) for t in range(T)], M, n, maxiter, opt, ar, ph, B0=B0)
 
 
 def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_total=None, shard=None, knm_outs=None,
