@@ -241,8 +241,10 @@ int odx_knm_fwd_bwd2_q_t(const void* K, int64_t ldk, const void* Klo, int64_t ld
                          int64_t workspace_bytes, odx_stream_t stream);
 /* out[q] = K' (K v[q]), q = 0 .. nv - 1, 3 <= nv <= 8, from ONE read of a compact-format block (what a lambda path's CG
  * states share: odx.solver.falkon_fit_path).  V / out: nv f64 rows, ldv / ldo doubles apart (even, >= M), 16-byte aligned.
- * The vectors sit in LDS as f64, so the widths that exist are nv <= 8 up to M = 2524 and nv <= 4 up to M = 5084; the
- * workspace twin returns a negative value for any other (M, fmt, nv) and the call ODX_ERR_UNSUPPORTED.  Slab per workgroup
+ * The vectors sit whole in LDS as f64, so the widths that exist are nv <= 8 up to M = 2524 and nv <= 4 up to M = 5084; the
+ * workspace twin returns a negative value for any other (M, fmt, nv) and the call ODX_ERR_UNSUPPORTED.  For wider blocks
+ * (every M <= 20440) the same product of up to 8 vectors is the PAIR odx_knm_fwdn_q (T = K V) + odx_knm_bwdn_q (out = K' T)
+ * below: two reads of the block, each tiled as column bands so that no whole vector has to fit in LDS.  Slab per workgroup
  * and vector, fixed-order reduction: bitwise reproducible, no atomics. */
 int64_t odx_knm_fwd_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv);
 int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
@@ -257,6 +259,18 @@ int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo
 int64_t odx_knm_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv);
 int odx_knm_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
                    const double* W, int64_t ldw, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
+                   odx_stream_t stream);
+/* T[q * ldt + r] = sum_j K[r, j] V[q * ldv + j], q = 0 .. nv - 1, r < n, from ONE read of a compact-format block: the forward
+ * half of a CG pass over up to 8 states where their vectors do not fit in LDS whole (odx_knm_fwd_bwdn_q above); followed by
+ * odx_knm_bwdn_q with W = T it gives out[q] = K' (K V[q]) from two reads of the block (HipBackend.ktkn).  fmt ODX_KNM_U24 or
+ * ODX_KNM_BF16, 1 <= M <= 20440, 1 <= nv <= 8; the workspace twin returns a negative value for any other (M, fmt, nv) and the
+ * call ODX_ERR_UNSUPPORTED (no workspace is needed otherwise: the twin returns 0 and `workspace` may be NULL).  Rows of V and T
+ * 16-byte aligned, ldv >= M and ldt >= n even.  All sums in f64; the block is tiled as column bands of 1280 columns x row
+ * ranges, a band of V in LDS as f64, and the bands' partial row sums are added into T in band order by the lane that owns the
+ * cell: no atomics, bitwise reproducible.  Cells T[q][n:] are never written; n <= 0 writes nothing. */
+int64_t odx_knm_fwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv);
+int odx_knm_fwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
+                   const double* V, int64_t ldv, double* T, int64_t ldt, void* workspace, int64_t workspace_bytes,
                    odx_stream_t stream);
 /* out[r * ldo] = (float) sum_j K[r, j] alpha[j], r < n, over a stored block in any of the three formats (scores from the
  * block a fit streamed: one read of it instead of a second Gaussian contraction).  Accumulated in f64 in a fixed order

@@ -92,6 +92,8 @@ SIGNATURES = {
     "odx_knm_fwd_bwdn_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "odx_knm_bwdn_q_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "odx_knm_bwdn_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "odx_knm_fwdn_q_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "odx_knm_fwdn_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "odx_knm_mv": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _i64, _vp]),
     "odx_gauss_ktk_stream_h2_rows": (_i64, [_i64, _i32]),
     "odx_gauss_ktk_stream_h2_workspace_bytes": (_i64, [_i64, _i64, _i32]),

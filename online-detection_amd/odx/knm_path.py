@@ -2,8 +2,10 @@
 multi-output fit (solver.falkon_fit_multi: T label columns, which share the preconditioner too).
 
 ``PathOps`` is mixed into ``backend.HipBackend``.  It adds the pass over several vectors from one read of the block
-(``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, the existing one- and two-vector passes for the rest; on a
-streamed shard odx_gauss_ktk_stream_h2n, up to 16 vectors from one BUILD of K), the preconditioners of a lambda path
+(``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, the existing one- and two-vector passes for the rest; where the
+one-read pass does not exist — above M = 5084 — groups of up to 8 from TWO reads, ``kvn``: odx_knm_fwdn_q, then
+odx_knm_bwdn_q, when ``wide_pass_min`` is set; on a streamed shard odx_gauss_ktk_stream_h2n, up to 16 vectors from one BUILD
+of K), the preconditioners of a lambda path
 (``precond_path``: odx_falkon_precond_path_f64), the right-hand sides of several label columns from one read of the block
 (``ktwn``: odx_knm_bwdn_q) and the triangular products of several vectors from one read of a factor (``trmvn``:
 odx_trmvn_f64), all HIP through libodx.
@@ -21,9 +23,20 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _aligned_rows(*ts):
+    return all(t.stride(0) % 2 == 0 and t.data_ptr() % 16 == 0 for t in ts)
+
+
 class PathOps:
-    """ktkn / ktkn_width / ktkn_span / precond_path of HipBackend.  On a streamed shard (KnmStream) ktkn makes ONE build of K
-    per group of ktkn_span = 16 vectors; ktkn_width keeps meaning vectors per READ of the block or ring (2 there)."""
+    """ktkn / ktkn_width / ktkn_span / kvn / precond_path of HipBackend.  On a streamed shard (KnmStream) ktkn makes ONE build
+    of K per group of ktkn_span = 16 vectors; ktkn_width keeps meaning vectors per READ of the block or ring (2 there)."""
+
+    # The smallest group of vectors that ktkn sends through the two-read route (odx_knm_fwdn_q + odx_knm_bwdn_q, up to 8
+    # vectors per two reads) on a compact block whose one-read width is 2 or 1; None: never (pairs and singles as before).
+    # An attribute, not an option: A/B runs and tests switch it on the backend.  profiles/wide_pass.md has the figures
+    # behind the value.
+    wide_pass_min = None
+    WIDE_PASS_MAX = 8           # vectors per call of odx_knm_fwdn_q / odx_knm_bwdn_q
 
     def _ktkn_bytes(self, K, nv):
         return self.lib.odx_knm_fwd_bwdn_q_workspace_bytes(max(K.n, 1), K.M, _CODE[K.fmt], nv)
@@ -56,12 +69,79 @@ class PathOps:
                                                     _p(Zf.meta), _p(Zf.sq), K.M, F.D, K.sigma, g, _p(V[l]), V.stride(0), _p(out[l]),
                                                     out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_ktk_stream_h2n")
 
+    def _ktkn_plan(self, K, L):
+        """The calls ktkn makes for L vectors over a stored block, in order: (kind, first vector, count) with kind "nv"
+        (odx_knm_fwd_bwdn_q: one read), "wide" (odx_knm_fwdn_q + odx_knm_bwdn_q: two reads), "pair" (ktk2: one read) or
+        "single" (one ktk per vector: one read each).  Uses ktkn_width, can_ktk2 and wide_pass_min only."""
+        width = self.ktkn_width(K)
+        plan, l = [], 0
+        wmin = self.wide_pass_min
+        if wmin is not None and width <= 2 and K.fmt in _CODE:
+            while L - l >= max(int(wmin), 1):
+                g = min(self.WIDE_PASS_MAX, L - l)
+                plan.append(("wide", l, g))
+                l += g
+        while l < L:
+            g = min(width, L - l)
+            plan.append(("nv" if g >= 3 else "pair" if g == 2 and self.can_ktk2(K) else "single", l, g))
+            l += g
+        return plan
+
+    def ktkn_reads(self, K, L):
+        """The number of reads of the block ktkn(K, V) makes for L vectors (on a streamed shard: the number of BUILDS of K;
+        a single vector there goes through ktk, one build)."""
+        if K.fmt == "stream":
+            return -(-L // self.ktkn_span(K))
+        return sum({"nv": 1, "wide": 2, "pair": 1, "single": g}[kind] for kind, _, g in self._ktkn_plan(K, L))
+
+    def kvn(self, K, V, out=None):
+        """out[l] = K V[l] (the row products, f64) for the L >= 1 rows of V ((L, >= M) f64) over a compact stored block: groups
+        of up to 8 rows from ONE read each (odx_knm_fwdn_q, every M <= 20440).  out: (L, >= roundup(n, 2)) f64; cells [n:]
+        of a row are not written.  Rows of V and out must be 16-byte aligned.  f32 blocks and streamed shards: ValueError
+        (the entry is not built for them)."""
+        if K.fmt not in _CODE:
+            raise ValueError("kvn: compact stored blocks only (u24 / bf16), got %r" % (K.fmt,))
+        L, M, n = V.shape[0], K.M, K.n
+        if out is None:
+            out = torch.zeros((L, (n + 1) // 2 * 2), dtype=torch.float64, device=self.device)
+        for t, cols in ((V, M), (out, n)):
+            if t.dim() != 2 or t.shape[0] != L or t.shape[1] < cols or t.dtype != torch.float64 or t.stride(1) != 1:
+                raise ValueError("kvn: V must be a (L, >= M) and out a (L, >= n) f64 matrix with contiguous rows")
+        if not _aligned_rows(V, out):
+            raise ValueError("kvn: rows of V and out must be 16-byte aligned (even leading dimension)")
+        for l in range(0, L if n > 0 else 0, self.WIDE_PASS_MAX):
+            g = min(self.WIDE_PASS_MAX, L - l)
+            if self.lib.odx_knm_fwdn_q_workspace_bytes(max(n, 1), M, _CODE[K.fmt], g) < 0:
+                raise hip.OdxError("odx_knm_fwdn_q: M = %d is outside the supported range (M <= 20440)" % M)
+            hip.check(self.lib.odx_knm_fwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], n, M, g,
+                                              _p(V[l]), V.stride(0), _p(out[l]), out.stride(0), None, 0, self._stream()),
+                      "odx_knm_fwdn_q")
+        return out
+
+    def _ktkn_wide(self, K, V, out, l, g):
+        """Rows [l, l + g) of V, g <= 8, from two reads of the block: T = K V (odx_knm_fwdn_q), out = K' T (odx_knm_bwdn_q).
+        T has a workspace of its own: "ktk" holds the backward kernel's slabs."""
+        n, M = K.n, K.M
+        ldt = (max(n, 1) + 1) // 2 * 2
+        T = self._workspace("ktkn_t", g * ldt * 8)[:g * ldt * 8].view(torch.float64).view(g, ldt)
+        self.kvn(K, V[l:l + g], out=T)
+        nbytes = self.lib.odx_knm_bwdn_q_workspace_bytes(max(n, 1), M, _CODE[K.fmt], g)
+        if nbytes < 0:
+            raise hip.OdxError("odx_knm_bwdn_q: M = %d is outside the supported range (M <= 20440)" % M)
+        ws = self._workspace("ktk", nbytes)
+        hip.check(self.lib.odx_knm_bwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], n, M, g,
+                                          _p(T), ldt, _p(out[l]), out.stride(0), _p(ws), ws.numel(), self._stream()),
+                  "odx_knm_bwdn_q")
+
     def ktkn(self, K, V, out=None):
         """out[l] = K' (K V[l]) for the L >= 1 rows of V ((L, ld) f64), with as few reads of K as its width allows: groups of
         ktkn_width(K) rows, a group of 3 .. 8 by odx_knm_fwd_bwdn_q, of 2 by ktk2 (two ktk where the block has no two-vector
-        pass), of 1 by ktk.  A streamed shard: groups of ktkn_span(K) = 16 rows, each from ONE build of K
-        (odx_gauss_ktk_stream_h2n; a single row goes through ktk).  Columns [0, K.M) of V / out are used; rows must be 16-byte
-        aligned for groups of 3 or more (on a streamed shard: of 2 or more)."""
+        pass), of 1 by ktk.  Where one read serves two vectors at most (M > 5084) and wide_pass_min is set, groups of
+        wide_pass_min or more rows go in chunks of up to 8 through TWO reads each (odx_knm_fwdn_q, then odx_knm_bwdn_q);
+        what remains below wide_pass_min keeps the pairs and singles.  ktkn_reads(K, L) counts the reads.  A streamed shard:
+        groups of ktkn_span(K) = 16 rows, each from ONE build of K (odx_gauss_ktk_stream_h2n; a single row goes through
+        ktk).  Columns [0, K.M) of V / out are used; rows must be 16-byte aligned for groups of 3 or more (on a streamed
+        shard: of 2 or more)."""
         L, M = V.shape[0], K.M
         if out is None:
             out = torch.zeros((L, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
@@ -79,17 +159,18 @@ class PathOps:
                     raise ValueError("ktkn: rows of V and out must be 16-byte aligned (even leading dimension)")
                 self._ktkn_stream(K, V, out, l, g)
             return out
-        width = self.ktkn_width(K)
-        for l in range(0, L, width):
-            g = min(width, L - l)
-            if g >= 3:
+        for kind, l, g in self._ktkn_plan(K, L):
+            if kind in ("nv", "wide"):
                 if V.stride(0) % 2 or out.stride(0) % 2 or V[l].data_ptr() % 16 or out[l].data_ptr() % 16:
                     raise ValueError("ktkn: rows of V and out must be 16-byte aligned (even leading dimension)")
+            if kind == "wide":
+                self._ktkn_wide(K, V, out, l, g)
+            elif kind == "nv":
                 ws = self._workspace("ktk", self._ktkn_bytes(K, g))
                 hip.check(self.lib.odx_knm_fwd_bwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], K.n, M, g,
                                                       _p(V[l]), V.stride(0), _p(out[l]), out.stride(0), _p(ws), ws.numel(),
                                                       self._stream()), "odx_knm_fwd_bwdn_q")
-            elif g == 2 and self.can_ktk2(K):
+            elif kind == "pair":
                 self.ktk2(K, V[l, :M], V[l + 1, :M], out1=out[l, :M], out2=out[l + 1, :M])
             else:
                 for j in range(l, l + g):
