@@ -154,32 +154,19 @@ static int bw_bands(int64_t M) { return (int)ceil_div(ceil_div(M, (int64_t)QCW),
 
 // row-range workgroups per band: the grid fills `cus` compute units BW_WPC times over (monotone in cus: the workspace is
 // sized for the device's, a launch may be confined to fewer)
-static int bw_nvt(int nv) { return nv <= 2 ? 2 : nv <= 4 ? 4 : 8; }      // the instantiated width that serves nv
-
 static int bw_ranges(int64_t n, int64_t M, int nv, int cus) {
   int64_t G = ceil_div((int64_t)cus * BW_WPC, (int64_t)bw_bands(M));
-  const int64_t nfull = n / bw_rows(bw_nvt(nv));      // whole row blocks (the rows behind them go to the first range)
+  const int64_t nfull = n / bw_rows(q_nvt(nv));      // whole row blocks (the rows behind them go to the first range)
   if (G > nfull) G = nfull;
   return (int)(G < 1 ? 1 : G);
 }
 
-static bool bw_supported(int64_t M, int fmt, int nv) {
-  return (fmt == ODX_KNM_U24 || fmt == ODX_KNM_BF16) && M > 0 && M <= 20440 && nv >= 1 && nv <= 8;
-}
-
-template <int NV, int FMT>
-static void launch_bwdnv(dim3 grid, hipStream_t s, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int64_t n, int64_t M,
-                         int nv, const double* W, int64_t ldw, double* slab, int64_t slab_ld) {
-  hipLaunchKernelGGL((knm_bwdnv_kernel<NV, FMT>), grid, dim3(BW_NT), 0, s, static_cast<const unsigned short*>(K), ldk,
-                     static_cast<const unsigned char*>(Klo), ldlo, n, M, nv, W, ldw, slab, slab_ld);
-}
-
-template <int FMT>
-static void dispatch_bwdnv(dim3 grid, hipStream_t s, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int64_t n, int64_t M,
-                           int nv, const double* W, int64_t ldw, double* slab, int64_t slab_ld) {
-  if (bw_nvt(nv) == 2) launch_bwdnv<2, FMT>(grid, s, K, ldk, Klo, ldlo, n, M, nv, W, ldw, slab, slab_ld);
-  else if (bw_nvt(nv) == 4) launch_bwdnv<4, FMT>(grid, s, K, ldk, Klo, ldlo, n, M, nv, W, ldw, slab, slab_ld);
-  else launch_bwdnv<8, FMT>(grid, s, K, ldk, Klo, ldlo, n, M, nv, W, ldw, slab, slab_ld);
+// launch(kernel) for the instantiated width that serves nv
+template <int FMT, typename Launch>
+static int dispatch_bwdnv(int nv, Launch&& launch) {
+  if (q_nvt(nv) == 2) return launch(knm_bwdnv_kernel<2, FMT>);
+  if (q_nvt(nv) == 4) return launch(knm_bwdnv_kernel<4, FMT>);
+  return launch(knm_bwdnv_kernel<8, FMT>);
 }
 
 }  // namespace odx
@@ -187,21 +174,15 @@ static void dispatch_bwdnv(dim3 grid, hipStream_t s, const void* K, int64_t ldk,
 using namespace odx;
 
 extern "C" int64_t odx_knm_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv) {
-  if (!bw_supported(M, fmt, nv)) return ODX_ERR_UNSUPPORTED;
+  if (!q_nv_supported(M, fmt, nv)) return ODX_ERR_UNSUPPORTED;
   if (n <= 0) return 0;
-  int cus = odx_device_cus();       // (never less than what a partitioned launch needs)
-  if (cus <= 0) cus = 256;
-  return (int64_t)nv * bw_ranges(n, M, nv, cus) * round_up(M, 4) * (int64_t)sizeof(double);
+  return (int64_t)nv * bw_ranges(n, M, nv, workspace_cus()) * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
 extern "C" int odx_knm_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
                               const double* W, int64_t ldw, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
                               odx_stream_t stream) {
-  if (!bw_supported(M, fmt, nv)) {
-    set_error("odx_knm_bwdn_q: needs ODX_KNM_U24 or ODX_KNM_BF16, 1 <= M <= 20440 and 1 <= nv <= 8 (got fmt %d, M %lld, nv %d)", fmt,
-              (long long)M, nv);
-    return ODX_ERR_UNSUPPORTED;
-  }
+  ODX_REQUIRE_Q_NV("odx_knm_bwdn_q", M, fmt, nv);
   ODX_REQUIRE(out && aligned16(out) && ldo % 2 == 0 && ldo >= M, "odx_knm_bwdn_q: out must be 16-byte aligned with even ldo >= M");
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
@@ -212,18 +193,15 @@ extern "C" int odx_knm_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64
   ODX_PROPAGATE(check_q_block("odx_knm_bwdn_q", K, ldk, Klo, ldlo, fmt, M));
   const int G = bw_ranges(n, M, nv, pass_cus());
   const int64_t slab_ld = round_up(M, 4);
-  if (workspace == nullptr || workspace_bytes < (int64_t)nv * G * slab_ld * (int64_t)sizeof(double)) {
-    set_error("odx_knm_bwdn_q: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
+  ODX_PROPAGATE(require_workspace("odx_knm_bwdn_q", workspace, workspace_bytes, (int64_t)nv * G * slab_ld * (int64_t)sizeof(double)));
   ODX_REQUIRE(G < 65536, "odx_knm_bwdn_q: too many row ranges");
   double* slab = static_cast<double*>(workspace);
   const dim3 grid((unsigned)bw_bands(M), (unsigned)G);
-  if (fmt == ODX_KNM_U24) dispatch_bwdnv<QF_U24>(grid, s, K, ldk, Klo, ldlo, n, M, nv, W, ldw, slab, slab_ld);
-  else dispatch_bwdnv<QF_BF16>(grid, s, K, ldk, nullptr, 0, n, M, nv, W, ldw, slab, slab_ld);
+  ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
+    return dispatch_bwdnv<decltype(f)::value>(nv, [&](auto* kernel) {
+      return q_launch(kernel, grid, BW_NT, 0, s, b.hi, b.ldk, b.lo, b.ldlo, b.n, b.M, nv, W, ldw, slab, slab_ld);
+    });
+  }));
   ODX_CHECK_LAUNCH("odx_knm_bwdn_q");
-  int64_t Ms[8];
-  int nslab[8];
-  for (int q = 0; q < nv; ++q) Ms[q] = M, nslab[q] = G;
-  return slab_reduce_batched_f64(nv, Ms, nslab, slab, slab_ld, (int64_t)G * slab_ld, out, ldo, s);
+  return reduce_nv(nv, M, G, slab, slab_ld, out, ldo, s);
 }

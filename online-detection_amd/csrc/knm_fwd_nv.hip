@@ -182,29 +182,12 @@ __global__ __launch_bounds__(FW_NT, 2) void knm_fwdnv_kernel(const unsigned shor
   }
 }
 
-static bool fw_supported(int64_t M, int fmt, int nv) {
-  return (fmt == ODX_KNM_U24 || fmt == ODX_KNM_BF16) && M > 0 && M <= 20440 && nv >= 1 && nv <= 8;
-}
-
-static int fw_nvt(int nv) { return nv <= 2 ? 2 : nv <= 4 ? 4 : 8; }      // the instantiated width that serves nv
-
-template <int NV, int FMT>
-static int launch_fwdnv(int grid, hipStream_t s, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int64_t n, int64_t M,
-                        int nv, const double* V, int64_t ldv, double* T, int64_t ldt) {
-  const size_t lds = (size_t)NV * FW_BCOLS * sizeof(double);
-  ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_fwdnv_kernel<NV, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-  hipLaunchKernelGGL((knm_fwdnv_kernel<NV, FMT>), dim3(grid), dim3(FW_NT), lds, s, static_cast<const unsigned short*>(K), ldk,
-                     static_cast<const unsigned char*>(Klo), ldlo, n, M, nv, V, ldv, T, ldt);
-  return ODX_OK;
-}
-
-template <int FMT>
-static int dispatch_fwdnv(int grid, hipStream_t s, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int64_t n, int64_t M,
-                          int nv, const double* V, int64_t ldv, double* T, int64_t ldt) {
-  if (fw_nvt(nv) == 2) return launch_fwdnv<2, FMT>(grid, s, K, ldk, Klo, ldlo, n, M, nv, V, ldv, T, ldt);
-  if (fw_nvt(nv) == 4) return launch_fwdnv<4, FMT>(grid, s, K, ldk, Klo, ldlo, n, M, nv, V, ldv, T, ldt);
-  return launch_fwdnv<8, FMT>(grid, s, K, ldk, Klo, ldlo, n, M, nv, V, ldv, T, ldt);
+// launch(kernel) for the instantiated width that serves nv
+template <int FMT, typename Launch>
+static int dispatch_fwdnv(int nv, Launch&& launch) {
+  if (q_nvt(nv) == 2) return launch(knm_fwdnv_kernel<2, FMT>);
+  if (q_nvt(nv) == 4) return launch(knm_fwdnv_kernel<4, FMT>);
+  return launch(knm_fwdnv_kernel<8, FMT>);
 }
 
 }  // namespace odx
@@ -214,19 +197,14 @@ using namespace odx;
 // (no workspace: the band partials are added into T itself, by the lane that owns the cell)
 extern "C" int64_t odx_knm_fwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv) {
   (void)n;
-  if (!fw_supported(M, fmt, nv)) return ODX_ERR_UNSUPPORTED;
-  return 0;
+  return q_nv_supported(M, fmt, nv) ? 0 : ODX_ERR_UNSUPPORTED;
 }
 
 extern "C" int odx_knm_fwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
                               const double* V, int64_t ldv, double* T, int64_t ldt, void* workspace, int64_t workspace_bytes,
                               odx_stream_t stream) {
   (void)workspace, (void)workspace_bytes;
-  if (!fw_supported(M, fmt, nv)) {
-    set_error("odx_knm_fwdn_q: needs ODX_KNM_U24 or ODX_KNM_BF16, 1 <= M <= 20440 and 1 <= nv <= 8 (got fmt %d, M %lld, nv %d)", fmt,
-              (long long)M, nv);
-    return ODX_ERR_UNSUPPORTED;
-  }
+  ODX_REQUIRE_Q_NV("odx_knm_fwdn_q", M, fmt, nv);
   ODX_REQUIRE(T && aligned16(T) && ldt % 2 == 0 && ldt >= n, "odx_knm_fwdn_q: T must be 16-byte aligned with even ldt >= n");
   if (n <= 0) return ODX_OK;
   ODX_REQUIRE(V && aligned16(V) && ldv % 2 == 0 && ldv >= M, "odx_knm_fwdn_q: V must be 16-byte aligned with even ldv >= M");
@@ -234,8 +212,12 @@ extern "C" int odx_knm_fwdn_q(const void* K, int64_t ldk, const void* Klo, int64
   hipStream_t s = as_stream(stream);
   const int64_t need = ceil_div(ceil_div(n, (int64_t)FW_R), (int64_t)(FW_NT / 64));      // workgroups that give every wave one row group
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)pass_cus() * FW_WPC));
-  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_fwdnv<QF_U24>(grid, s, K, ldk, Klo, ldlo, n, M, nv, V, ldv, T, ldt)));
-  else ODX_PROPAGATE((dispatch_fwdnv<QF_BF16>(grid, s, K, ldk, nullptr, 0, n, M, nv, V, ldv, T, ldt)));
+  const size_t lds = (size_t)q_nvt(nv) * FW_BCOLS * sizeof(double);      // a band of the vectors of the instantiated width
+  ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
+    return dispatch_fwdnv<decltype(f)::value>(nv, [&](auto* kernel) {
+      return q_launch(kernel, dim3(grid), FW_NT, lds, s, b.hi, b.ldk, b.lo, b.ldlo, b.n, b.M, nv, V, ldv, T, ldt);
+    });
+  }));
   ODX_CHECK_LAUNCH("odx_knm_fwdn_q");
   return ODX_OK;
 }

@@ -242,7 +242,7 @@ static int64_t nv_lds_bytes(const NvCfg& c, int64_t chunks) {
 static bool pick_nvcfg(int64_t M, int nv, NvCfg* cfg) {
   if (M <= 0 || nv < 3 || nv > 8) return false;
   const int64_t chunks = (M + 3) / 4;
-  const int nvt = nv <= 4 ? 4 : 8;
+  const int nvt = q_nvt(nv);
   NvCfg c;
   if (nvt == 8) {
     if (chunks <= 256) c = {256, 1, 4, 8, 2};
@@ -268,21 +268,10 @@ static int nvgrid_for(const NvCfg& cfg, int64_t n, int cus) {
   return (int)(g < 1 ? 1 : g);
 }
 
-template <int NT, int CH, int R, int NV, int FMT>
-static int launch_passnv(int grid, size_t lds, hipStream_t s, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int64_t n,
-                         int64_t M, int nv, const double* V, int64_t ldv, double* slab, int64_t slab_ld) {
-  ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_passnv_kernel<NT, CH, R, NV, FMT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((knm_passnv_kernel<NT, CH, R, NV, FMT>), dim3(grid), dim3(NT), lds, s, static_cast<const unsigned short*>(K), ldk,
-                     static_cast<const unsigned char*>(Klo), ldlo, n, M, nv, V, ldv, slab, slab_ld);
-  return ODX_OK;
-}
-
-template <int FMT>
-static int dispatch_passnv(const NvCfg& cfg, int grid, size_t lds, hipStream_t s, const void* K, int64_t ldk, const void* Klo,
-                           int64_t ldlo, int64_t n, int64_t M, int nv, const double* V, int64_t ldv, double* slab, int64_t slab_ld) {
-#define ODX_NV(NT_, CH_, R_, NV_) return launch_passnv<NT_, CH_, R_, NV_, FMT>(grid, lds, s, K, ldk, Klo, ldlo, n, M, nv, V, ldv, slab, slab_ld)
-  // (exactly the configurations pick_nvcfg hands out)
+// launch(kernel, threads) for the instantiation cfg names: exactly the configurations pick_nvcfg hands out
+template <int FMT, typename Launch>
+static int dispatch_passnv(const NvCfg& cfg, Launch&& launch) {
+#define ODX_NV(NT_, CH_, R_, NV_) return launch(knm_passnv_kernel<NT_, CH_, R_, NV_, FMT>, NT_)
   if (cfg.nvt == 8) {
     if (cfg.nt == 256) ODX_NV(256, 1, 4, 8);
     if (cfg.ch == 1) ODX_NV(512, 1, 4, 8);
@@ -301,11 +290,9 @@ using namespace odx;
 
 extern "C" int64_t odx_knm_fwd_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv) {
   NvCfg cfg;
-  if ((fmt != ODX_KNM_U24 && fmt != ODX_KNM_BF16) || !pick_nvcfg(M, nv, &cfg)) return ODX_ERR_UNSUPPORTED;
+  if (!q_format(fmt) || !pick_nvcfg(M, nv, &cfg)) return ODX_ERR_UNSUPPORTED;
   if (n <= 0) return 0;
-  int cus = odx_device_cus();       // (never less than what a partitioned launch needs)
-  if (cus <= 0) cus = 256;
-  return (int64_t)nv * cus * cfg.wg_per_cu * round_up(M, 4) * (int64_t)sizeof(double);
+  return (int64_t)nv * workspace_cus() * cfg.wg_per_cu * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
 extern "C" int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
@@ -327,17 +314,14 @@ extern "C" int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, i
   }
   const int grid = nvgrid_for(cfg, n, pass_cus());
   const int64_t slab_ld = round_up(M, 4);
-  if (workspace == nullptr || workspace_bytes < (int64_t)nv * grid * slab_ld * (int64_t)sizeof(double)) {
-    set_error("odx_knm_fwd_bwdn_q: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
+  ODX_PROPAGATE(require_workspace("odx_knm_fwd_bwdn_q", workspace, workspace_bytes, (int64_t)nv * grid * slab_ld * (int64_t)sizeof(double)));
   double* slab = static_cast<double*>(workspace);
   const size_t lds = (size_t)nv_lds_bytes(cfg, (M + 3) / 4);
-  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_passnv<QF_U24>(cfg, grid, lds, s, K, ldk, Klo, ldlo, n, M, nv, V, ldv, slab, slab_ld)));
-  else ODX_PROPAGATE((dispatch_passnv<QF_BF16>(cfg, grid, lds, s, K, ldk, nullptr, 0, n, M, nv, V, ldv, slab, slab_ld)));
+  ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
+    return dispatch_passnv<decltype(f)::value>(cfg, [&](auto* kernel, int threads) {
+      return q_launch(kernel, dim3(grid), threads, lds, s, b.hi, b.ldk, b.lo, b.ldlo, b.n, b.M, nv, V, ldv, slab, slab_ld);
+    });
+  }));
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwdn_q");
-  int64_t Ms[8];
-  int nslab[8];
-  for (int q = 0; q < nv; ++q) Ms[q] = M, nslab[q] = grid;
-  return slab_reduce_batched_f64(nv, Ms, nslab, slab, slab_ld, (int64_t)grid * slab_ld, out, ldo, s);
+  return reduce_nv(nv, M, grid, slab, slab_ld, out, ldo, s);
 }

@@ -483,11 +483,7 @@ static bool pick_qcfg(int64_t M, int nv, int fmt, QCfg* cfg) {
 // of the CU partition the passes' stream is confined to, odx_stream_create_cu_mask)
 static int g_pass_cus = 0;
 
-int pass_cus() {
-  if (g_pass_cus > 0) return g_pass_cus;
-  const int cus = odx_device_cus();
-  return cus > 0 ? cus : 256;
-}
+int pass_cus() { return g_pass_cus > 0 ? g_pass_cus : workspace_cus(); }
 
 static int qgrid_for(const QCfg& cfg, int64_t n) {
   const int cus = pass_cus();
@@ -498,38 +494,23 @@ static int qgrid_for(const QCfg& cfg, int64_t n) {
   return (int)g;
 }
 
-template <int NT, int CH, int R, int NV, int FMT, int WPE = (NT >= 1024 ? 4 : 2)>
-static int launch_passq(int grid, size_t lds, hipStream_t s, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int64_t n,
-                        int64_t M, const double* v, const double* v2, const double* w, double* slab, int64_t slab_ld, double* t_out) {
-  ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_passq_kernel<NT, CH, R, NV, FMT, WPE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((knm_passq_kernel<NT, CH, R, NV, FMT, WPE>), dim3(grid), dim3(NT), lds, s, static_cast<const unsigned short*>(K),
-                     ldk, static_cast<const unsigned char*>(Klo), ldlo, n, M, v, v2, w, slab, slab_ld, t_out);
-  return ODX_OK;
-}
-
+// The pass over block b with the kernel cfg names: exactly the configurations pick_qcfg hands out.  (v2: the second vector
+// of NV = 2; w: NV = 1 only.)
 template <int NV, int FMT>
-static int dispatch_passq(const QCfg& cfg, int grid, size_t lds, hipStream_t s, const void* K, int64_t ldk, const void* Klo,
-                          int64_t ldlo, int64_t n, int64_t M, const double* v, const double* v2, const double* w, double* slab,
-                          int64_t slab_ld, double* t_out) {
-#define ODX_Q(NT_, CH_, R_) return launch_passq<NT_, CH_, R_, NV, FMT>(grid, lds, s, K, ldk, Klo, ldlo, n, M, v, v2, w, slab, slab_ld, t_out)
+static int dispatch_passq(const QCfg& cfg, const QBlock& b, int grid, size_t lds, hipStream_t s, const double* v, const double* v2,
+                          const double* w, double* slab, int64_t slab_ld, double* t_out) {
+#define ODX_Q(NT_, CH_, R_)                                                                                                      \
+  return q_launch(knm_passq_kernel<NT_, CH_, R_, NV, FMT, (NT_ >= 1024 ? 4 : 2)>, dim3(grid), NT_, lds, s, b.hi, b.ldk, b.lo, b.ldlo, \
+                  b.n, b.M, v, v2, w, slab, slab_ld, t_out)
+#define ODX_QH(CH_, R_)                                                                                                          \
+  return q_launch(knm_passq_stag_kernel<CH_, R_, FMT>, dim3(grid), 512, lds, s, b.hi, b.ldk, b.lo, b.ldlo, b.n, b.M, v, w, slab,  \
+                  slab_ld, t_out)
   if constexpr (NV == 1) {
     if (cfg.nt == 0) {
-#define ODX_QH(CH_, R_)                                                                                                         \
-  do {                                                                                                                          \
-    ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_passq_stag_kernel<CH_, R_, FMT>),                       \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                   \
-    hipLaunchKernelGGL((knm_passq_stag_kernel<CH_, R_, FMT>), dim3(grid), dim3(512), lds, s,                                    \
-                       static_cast<const unsigned short*>(K), ldk, static_cast<const unsigned char*>(Klo), ldlo, n, M, v, w,    \
-                       slab, slab_ld, t_out);                                                                                   \
-    return ODX_OK;                                                                                                              \
-  } while (0)
       if (cfg.ch == 2) ODX_QH(2, 8);
       if (cfg.ch == 4) ODX_QH(4, 4);
       ODX_QH(10, 2);
-#undef ODX_QH
     }
-    // (exactly the configurations pick_qcfg hands out)
     if (cfg.nt == 256 && cfg.ch == 1) ODX_Q(256, 1, 16);
     if (cfg.nt == 256 && cfg.ch == 8) ODX_Q(256, 8, 3);
     if (cfg.nt == 512 && cfg.ch == 6) ODX_Q(512, 6, 4);
@@ -539,6 +520,7 @@ static int dispatch_passq(const QCfg& cfg, int grid, size_t lds, hipStream_t s, 
     ODX_Q(512, 5, 2);
   }
 #undef ODX_Q
+#undef ODX_QH
 }
 
 int check_q_block(const char* who, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t M) {
@@ -581,7 +563,7 @@ static void passq_batch_geometry(int B, const int64_t* n, const int64_t* M, cons
 
 int64_t knm_passq_batched_workspace_bytes(int B, const int64_t* n, const int64_t* M, int fmt) {
   QCfg cfg;
-  if ((fmt != ODX_KNM_U24 && fmt != ODX_KNM_BF16) || !passq_batch_cfg(B, M, fmt, &cfg)) return ODX_ERR_UNSUPPORTED;
+  if (!q_format(fmt) || !passq_batch_cfg(B, M, fmt, &cfg)) return ODX_ERR_UNSUPPORTED;
   int gmax;
   int64_t slab_ld;
   passq_batch_geometry(B, n, M, cfg, &gmax, &slab_ld);
@@ -591,22 +573,10 @@ int64_t knm_passq_batched_workspace_bytes(int B, const int64_t* n, const int64_t
 template <int FMT>
 static int launch_passq_batched(const QCfg& cfg, const PassBatchQ& pb, int gmax, int B, size_t lds, hipStream_t s, const double* v,
                                 int64_t vstride, double* slab, int64_t slab_ld, int64_t slab_stride) {
-#define ODX_QB(NT_, CH_, R_)                                                                                                        \
-  do {                                                                                                                              \
-    ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_passq_batched_kernel<NT_, CH_, R_, FMT>),                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                        \
-    hipLaunchKernelGGL((knm_passq_batched_kernel<NT_, CH_, R_, FMT>), dim3(gmax, B), dim3(NT_), lds, s, pb, v, vstride, slab, slab_ld, \
-                       slab_stride);                                                                                                \
-    return ODX_OK;                                                                                                                  \
-  } while (0)
-#define ODX_QBH(CH_, R_)                                                                                                            \
-  do {                                                                                                                              \
-    ODX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knm_passq_stag_batched_kernel<CH_, R_, FMT>),                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                        \
-    hipLaunchKernelGGL((knm_passq_stag_batched_kernel<CH_, R_, FMT>), dim3(gmax, B), dim3(512), lds, s, pb, v, vstride, slab, slab_ld, \
-                       slab_stride);                                                                                                \
-    return ODX_OK;                                                                                                                  \
-  } while (0)
+#define ODX_QB(NT_, CH_, R_) \
+  return q_launch(knm_passq_batched_kernel<NT_, CH_, R_, FMT>, dim3(gmax, B), NT_, lds, s, pb, v, vstride, slab, slab_ld, slab_stride)
+#define ODX_QBH(CH_, R_) \
+  return q_launch(knm_passq_stag_batched_kernel<CH_, R_, FMT>, dim3(gmax, B), 512, lds, s, pb, v, vstride, slab, slab_ld, slab_stride)
   if (cfg.nt == 0 && cfg.ch == 2) ODX_QBH(2, 8);
   if (cfg.nt == 0 && cfg.ch == 4) ODX_QBH(4, 4);
   if (cfg.nt == 0 && cfg.ch == 10) ODX_QBH(10, 2);
@@ -626,17 +596,14 @@ int knm_passq_batched(int B, const void* const* Khi, const int64_t* ldk, const v
                       void* workspace, int64_t workspace_bytes, hipStream_t s) {
   ODX_REQUIRE(B >= 1 && B <= ODX_MAX_ZBATCH, "knm_passq_batched: 1..%d classes", ODX_MAX_ZBATCH);
   QCfg cfg;
-  ODX_REQUIRE((fmt == ODX_KNM_U24 || fmt == ODX_KNM_BF16) && passq_batch_cfg(B, M, fmt, &cfg),
+  ODX_REQUIRE(q_format(fmt) && passq_batch_cfg(B, M, fmt, &cfg),
               "knm_passq_batched: the classes of a batch must share one pass configuration");
   int gmax;
   int64_t slab_ld;
   passq_batch_geometry(B, n, M, cfg, &gmax, &slab_ld);
   const int per = cfg.nt == 0 ? 2 : 1;                            // the halves kernel leaves one vector per half
   const int64_t slab_stride = (int64_t)per * gmax * slab_ld;
-  if (workspace == nullptr || workspace_bytes < (int64_t)B * slab_stride * (int64_t)sizeof(double)) {
-    set_error("knm_passq_batched: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
+  ODX_PROPAGATE(require_workspace("knm_passq_batched", workspace, workspace_bytes, (int64_t)B * slab_stride * (int64_t)sizeof(double)));
   PassBatchQ pb;
   int nslab[ODX_MAX_ZBATCH];
   for (int b = 0; b < ODX_MAX_ZBATCH; ++b) {
@@ -686,17 +653,11 @@ extern "C" int odx_set_pass_cus(int cus) {
   return ODX_OK;
 }
 
-static int check_q(const char* who, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t M) {
-  return check_q_block(who, K, ldk, Klo, ldlo, fmt, M);
-}
-
 extern "C" int64_t odx_knm_fwd_bwd_q_workspace_bytes(int64_t n, int64_t M, int fmt) {
   QCfg cfg;
   if (n <= 0 || M <= 0) return 0;
-  if ((fmt != ODX_KNM_U24 && fmt != ODX_KNM_BF16) || !pick_qcfg(M, 1, fmt, &cfg)) return ODX_ERR_UNSUPPORTED;
-  int cus = odx_device_cus();       // (never less than what a partitioned launch needs)
-  if (cus <= 0) cus = 256;
-  return (int64_t)cus * (cfg.nt == 0 ? 2 * cfg.wg_per_cu : cfg.wg_per_cu) * round_up(M, 4) * (int64_t)sizeof(double);
+  if (!q_format(fmt) || !pick_qcfg(M, 1, fmt, &cfg)) return ODX_ERR_UNSUPPORTED;
+  return (int64_t)workspace_cus() * (cfg.nt == 0 ? 2 * cfg.wg_per_cu : cfg.wg_per_cu) * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
 // (t_out: the _t entry's extra output, null for the plain one — same kernels, same slabs, same out either way)
@@ -710,24 +671,23 @@ static int knm_fwd_bwd_q_impl(const void* K, int64_t ldk, const void* Klo, int64
     return ODX_OK;
   }
   ODX_REQUIRE(v || w, "odx_knm_fwd_bwd_q: both v and w null");
-  ODX_PROPAGATE(check_q("odx_knm_fwd_bwd_q", K, ldk, Klo, ldlo, fmt, M));
+  ODX_PROPAGATE(check_q_block("odx_knm_fwd_bwd_q", K, ldk, Klo, ldlo, fmt, M));
   QCfg cfg;
   if (!pick_qcfg(M, 1, fmt, &cfg)) {
-    set_error("odx_knm_fwd_bwd_q: M = %lld exceeds the 20440 columns the compact-format pass kernels are built for", (long long)M);
+    set_error("odx_knm_fwd_bwd_q: M = %lld exceeds the %lld columns the compact-format pass kernels are built for", (long long)M,
+              (long long)Q_MAX_M);
     return ODX_ERR_UNSUPPORTED;
   }
   const int grid = qgrid_for(cfg, n);
   const int64_t slab_ld = round_up(M, 4);
   const int nslab = cfg.nt == 0 ? 2 * grid : grid;       // the staggered kernel leaves one vector per half
-  if (workspace == nullptr || workspace_bytes < (int64_t)nslab * slab_ld * (int64_t)sizeof(double)) {
-    set_error("odx_knm_fwd_bwd_q: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
+  ODX_PROPAGATE(require_workspace("odx_knm_fwd_bwd_q", workspace, workspace_bytes, (int64_t)nslab * slab_ld * (int64_t)sizeof(double)));
   double* slab = static_cast<double*>(workspace);
   // (the halves kernel keeps v zero-filled up to the 10 x 256 chunks of four its threads walk)
   const size_t lds = (cfg.nt == 0 ? (size_t)(cfg.ch * 256 * 4) : (size_t)(slab_ld + 4)) * sizeof(double);      // + the zero chunk
-  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_passq<1, QF_U24>(cfg, grid, lds, s, K, ldk, Klo, ldlo, n, M, v, nullptr, w, slab, slab_ld, t_out)));
-  else ODX_PROPAGATE((dispatch_passq<1, QF_BF16>(cfg, grid, lds, s, K, ldk, nullptr, 0, n, M, v, nullptr, w, slab, slab_ld, t_out)));
+  ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
+    return dispatch_passq<1, decltype(f)::value>(cfg, b, grid, lds, s, v, nullptr, w, slab, slab_ld, t_out);
+  }));
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwd_q");
   return slab_reduce_f64(slab, slab_ld, nslab, M, out, s);
 }
@@ -748,10 +708,8 @@ extern "C" int odx_knm_fwd_bwd_q_t(const void* K, int64_t ldk, const void* Klo, 
 extern "C" int64_t odx_knm_fwd_bwd2_q_workspace_bytes(int64_t n, int64_t M, int fmt) {
   QCfg cfg;
   if (n <= 0 || M <= 0) return 0;
-  if ((fmt != ODX_KNM_U24 && fmt != ODX_KNM_BF16) || !pick_qcfg(M, 2, fmt, &cfg)) return ODX_ERR_UNSUPPORTED;
-  int cus = odx_device_cus();
-  if (cus <= 0) cus = 256;
-  return 2 * (int64_t)cus * cfg.wg_per_cu * round_up(M, 4) * (int64_t)sizeof(double);
+  if (!q_format(fmt) || !pick_qcfg(M, 2, fmt, &cfg)) return ODX_ERR_UNSUPPORTED;
+  return 2 * (int64_t)workspace_cus() * cfg.wg_per_cu * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
 static int knm_fwd_bwd2_q_impl(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
@@ -765,7 +723,7 @@ static int knm_fwd_bwd2_q_impl(const void* K, int64_t ldk, const void* Klo, int6
     return ODX_OK;
   }
   ODX_REQUIRE(v && v2, "odx_knm_fwd_bwd2_q: null v or v2");
-  ODX_PROPAGATE(check_q("odx_knm_fwd_bwd2_q", K, ldk, Klo, ldlo, fmt, M));
+  ODX_PROPAGATE(check_q_block("odx_knm_fwd_bwd2_q", K, ldk, Klo, ldlo, fmt, M));
   QCfg cfg;
   if (!pick_qcfg(M, 2, fmt, &cfg)) {
     set_error("odx_knm_fwd_bwd2_q: M = %lld is outside the two-vector configurations (use two single passes)", (long long)M);
@@ -773,14 +731,12 @@ static int knm_fwd_bwd2_q_impl(const void* K, int64_t ldk, const void* Klo, int6
   }
   const int grid = qgrid_for(cfg, n);
   const int64_t slab_ld = round_up(M, 4);
-  if (workspace == nullptr || workspace_bytes < 2 * (int64_t)grid * slab_ld * (int64_t)sizeof(double)) {
-    set_error("odx_knm_fwd_bwd2_q: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
+  ODX_PROPAGATE(require_workspace("odx_knm_fwd_bwd2_q", workspace, workspace_bytes, 2 * (int64_t)grid * slab_ld * (int64_t)sizeof(double)));
   double* slab = static_cast<double*>(workspace);
   const size_t lds = (size_t)(2 * (slab_ld + 4) * sizeof(double));      // two vectors, each with its zero chunk
-  if (fmt == ODX_KNM_U24) ODX_PROPAGATE((dispatch_passq<2, QF_U24>(cfg, grid, lds, s, K, ldk, Klo, ldlo, n, M, v, v2, nullptr, slab, slab_ld, t_out)));
-  else ODX_PROPAGATE((dispatch_passq<2, QF_BF16>(cfg, grid, lds, s, K, ldk, nullptr, 0, n, M, v, v2, nullptr, slab, slab_ld, t_out)));
+  ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
+    return dispatch_passq<2, decltype(f)::value>(cfg, b, grid, lds, s, v, v2, nullptr, slab, slab_ld, t_out);
+  }));
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwd2_q");
   return slab_reduce2_f64(slab, slab_ld, grid, M, out, out2, s);
 }

@@ -85,8 +85,10 @@ int knm_passq_batched(int B, const void* const* Khi, const int64_t* ldk, const v
                       const int64_t* n, const int64_t* M, const double* v, int64_t vstride, double* out, int64_t ostride,
                       void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
-// knm_pass_q.hip, shared with knm_pass_nv.hip: the compute units the persistent pass grids are sized for (the device's, or
-// odx_set_pass_cus), and the argument checks of a compact-format block
+// knm_pass_q.hip, shared with knm_pass_nv.hip, knm_bwd_nv.hip and knm_fwd_nv.hip.  pass_cus: the compute units the pass grids
+// of a LAUNCH are sized for (the device's, or the partition odx_set_pass_cus names; the workspace twins size for
+// workspace_cus() of knm_q.h, the whole device).  check_q_block: the argument checks of a compact-format block, the one
+// check every compact entry makes (the rest of the four files' shared host code is in knm_q.h).
 int pass_cus();
 int check_q_block(const char* who, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t M);
 

@@ -20,11 +20,7 @@ import os
 import torch
 
 from . import hip
-from .knm_path import PathOps
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+from .knm_path import PathOps, _p
 
 
 class Features:
@@ -106,9 +102,6 @@ class KnmStream:
     def __init__(self, F, Zf, sigma, ring=None):
         self.F, self.Zf, self.sigma, self.n, self.M, self.ring = F, Zf, float(sigma), F.n, Zf.n, ring
         self.K, self.fmt, self.lo = F.P, "stream", None
-
-
-_KNM_CODE = {"f32": hip.KNM_F32, "u24": hip.KNM_U24, "bf16": hip.KNM_BF16}
 
 
 class HipBackend(PathOps):
@@ -423,7 +416,7 @@ class HipBackend(PathOps):
         if self.gauss not in ("h2", "f8") or n <= 0 or M <= 0:
             return "f32"
         if self.knm_storage in ("u24", "bf16"):
-            return self.knm_storage if self.lib.odx_knm_fwd_bwd_q_workspace_bytes(n, M, _KNM_CODE[self.knm_storage]) >= 0 else "f32"
+            return self.knm_storage if self.lib.odx_knm_fwd_bwd_q_workspace_bytes(n, M, hip.KNM_CODE[self.knm_storage]) >= 0 else "f32"
         if self.knm_storage == "auto" and n * M >= (1 << 27) and M >= 1024 and (self.gauss == "f8" or self.lib.odx_gauss_h2_tile(n, M) == 256) \
                 and self.lib.odx_knm_fwd_bwd_q_workspace_bytes(n, M, hip.KNM_U24) >= 0:
             return "u24"
@@ -435,18 +428,12 @@ class HipBackend(PathOps):
         not grow with n."""
         if self.knm_format(n, M) == "stream":
             return max(0, int(self._stream_bytes(max(n, 1), M, 64 if D is None else D)))
-        return int(self.lib.odx_knm_bytes(max(n, 0), M, _KNM_CODE[self.knm_format(n, M)]))
-
-    def _stream_bytes(self, n, M, D):
-        nbytes = int(self.lib.odx_gauss_ktk_stream_h2_workspace_bytes(n, M, D))
-        if nbytes < 0:
-            raise hip.OdxError("odx_gauss_ktk_stream_h2: M = %d is outside the supported range (M <= 20440)" % M)
-        return nbytes
+        return int(self.lib.odx_knm_bytes(max(n, 0), M, hip.KNM_CODE[self.knm_format(n, M)]))
 
     def _knm_block(self, n, M, fmt, out):
         K = Knm()
         K.n, K.M, K.fmt = n, M, fmt
-        K.ld = ld = int(self.lib.odx_knm_ld(M, _KNM_CODE[fmt]))
+        K.ld = ld = int(self.lib.odx_knm_ld(M, hip.KNM_CODE[fmt]))
         per = {"f32": 4, "u24": 3, "bf16": 2}[fmt]
         need = n * ld * per
         if out is not None:
@@ -514,7 +501,7 @@ class HipBackend(PathOps):
                               (self.lib.odx_gauss_knm_h2_store, F.P, F.meta, Zf.P, Zf.meta))
         sqx, sqz = (F.sq8, Zf.sq8) if f8 else (F.sq, Zf.sq)
         hip.check(fn(_p(PX), PX.stride(0), _p(mx), _p(sqx), n, _p(PZ), PZ.stride(0), _p(mz), _p(sqz), M, F.D, float(sigma),
-                     _KNM_CODE[fmt], _p(K.K), K.ld, _p(K.lo), K.ld, _p(w), _p(rhs_out if w is not None else None), _p(ws),
+                     hip.KNM_CODE[fmt], _p(K.K), K.ld, _p(K.lo), K.ld, _p(w), _p(rhs_out if w is not None else None), _p(ws),
                      ws.numel() if ws is not None else 0, self._stream()), "odx_gauss_knm_f8_store" if f8 else "odx_gauss_knm_h2_store")
         return K, rhs_out
 
@@ -552,101 +539,6 @@ class HipBackend(PathOps):
     def reserve_cus_during_passes(self, cus):
         """Leave `cus` CUs free while the persistent CG pass kernel runs, for work queued on other streams."""
         hip.check(self.lib.odx_set_pass_reserved_cus(int(cus)), "odx_set_pass_reserved_cus")
-
-    def _ktk_stream(self, K, v, v2, w, out, out2):
-        """out = K' (K v + w) [, out2 = K' (K v2)] with K recomputed chunk by chunk (odx_gauss_ktk_stream_h2)."""
-        F, Zf = K.F, K.Zf
-        nbytes = self._stream_bytes(max(K.n, 1), K.M, F.D)
-        ws = K.ring if K.ring is not None else self._workspace("ktk_stream", nbytes)
-        hip.check(self.lib.odx_gauss_ktk_stream_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), K.n, _p(Zf.P), Zf.P.stride(0),
-                                                   _p(Zf.meta), _p(Zf.sq), K.M, F.D, K.sigma, _p(v), _p(v2), _p(w), _p(out),
-                                                   _p(out2), _p(ws), ws.numel(), self._stream()), "odx_gauss_ktk_stream_h2")
-
-    def _check_t_out(self, K, v, t_out):
-        if K.fmt == "stream":
-            raise ValueError("ktk: t_out needs a stored K_nM block (a streamed shard's rows pass in chunks)")
-        if v is None:
-            raise ValueError("ktk: t_out is the row product K v: it needs v")
-        if t_out.dtype != torch.float64 or t_out.numel() != K.n or not t_out.is_contiguous():
-            raise ValueError("ktk: t_out must be a contiguous f64 vector of the block's %d rows" % K.n)
-
-    def ktk(self, K, v=None, w=None, out=None, t_out=None):
-        """out = K' (K v + w) over this shard (f64).  t_out: optional (n,) f64 that receives the row products K v (before w
-        is added), a by-product of the same read of K (odx_knm_fwd_bwd[_q]_t); `out` is bitwise the same with or without it."""
-        if out is None:
-            out = torch.empty(K.M, dtype=torch.float64, device=self.device)
-        if t_out is not None:
-            self._check_t_out(K, v, t_out)
-        if K.fmt == "stream":
-            self._ktk_stream(K, v, None, w, out, None)
-            return out
-        if K.fmt != "f32":
-            code = _KNM_CODE[K.fmt]
-            nbytes = self.lib.odx_knm_fwd_bwd_q_workspace_bytes(max(K.n, 1), K.M, code)
-            if nbytes < 0:
-                raise hip.OdxError("odx_knm_fwd_bwd_q: M = %d is outside the supported range" % K.M)
-            ws = self._workspace("ktk", nbytes)
-            if t_out is not None:
-                hip.check(self.lib.odx_knm_fwd_bwd_q_t(_p(K.K), K.ld, _p(K.lo), K.ld, code, K.n, K.M, _p(v), _p(w), _p(out), _p(t_out),
-                                                       _p(ws), ws.numel(), self._stream()), "odx_knm_fwd_bwd_q_t")
-                return out
-            hip.check(self.lib.odx_knm_fwd_bwd_q(_p(K.K), K.ld, _p(K.lo), K.ld, code, K.n, K.M, _p(v), _p(w), _p(out), _p(ws),
-                                                 ws.numel(), self._stream()), "odx_knm_fwd_bwd_q")
-            return out
-        nbytes = self.lib.odx_knm_fwd_bwd_workspace_bytes(max(K.n, 1), K.M)
-        if nbytes < 0:
-            raise hip.OdxError("odx_knm_fwd_bwd: M = %d is outside the supported range" % K.M)
-        ws = self._workspace("ktk", nbytes)
-        if t_out is not None:
-            hip.check(self.lib.odx_knm_fwd_bwd_t(_p(K.K), K.ld, K.n, K.M, _p(v), _p(w), _p(out), _p(t_out), _p(ws), ws.numel(),
-                                                 self._stream()), "odx_knm_fwd_bwd_t")
-            return out
-        hip.check(self.lib.odx_knm_fwd_bwd(_p(K.K), K.ld, K.n, K.M, _p(v), _p(w), _p(out), _p(ws), ws.numel(),
-                                           self._stream()), "odx_knm_fwd_bwd")
-        return out
-
-    def _ktk2_bytes(self, K):
-        if K.fmt != "f32":
-            return self.lib.odx_knm_fwd_bwd2_q_workspace_bytes(max(K.n, 1), K.M, _KNM_CODE[K.fmt])
-        return self.lib.odx_knm_fwd_bwd2_workspace_bytes(max(K.n, 1), K.M)
-
-    def can_ktk2(self, K):
-        """Whether the two-vector pass exists at this block's width (both vectors must fit in LDS: M <= 10 000).  A streamed
-        shard always has one: each chunk is built once and read for both vectors while it is resident."""
-        return K.fmt == "stream" or self._ktk2_bytes(K) >= 0
-
-    def ktk2(self, K, v1, v2, out1=None, out2=None, t_out=None):
-        """out1 = K' (K v1), out2 = K' (K v2) over this shard from ONE read of K (odx_knm_fwd_bwd2[_q]).  t_out: optional
-        (n,) f64 that receives the row products K v1 (odx_knm_fwd_bwd2[_q]_t)."""
-        if t_out is not None:
-            self._check_t_out(K, v1, t_out)
-        if out1 is None:
-            out1 = torch.empty(K.M, dtype=torch.float64, device=self.device)
-        if out2 is None:
-            out2 = torch.empty(K.M, dtype=torch.float64, device=self.device)
-        if K.fmt == "stream":
-            self._ktk_stream(K, v1, v2, None, out1, out2)
-            return out1, out2
-        nbytes = self._ktk2_bytes(K)
-        if nbytes < 0:
-            raise hip.OdxError("odx_knm_fwd_bwd2: M = %d is outside the two-vector configurations" % K.M)
-        ws = self._workspace("ktk", nbytes)
-        if t_out is not None:
-            if K.fmt != "f32":
-                hip.check(self.lib.odx_knm_fwd_bwd2_q_t(_p(K.K), K.ld, _p(K.lo), K.ld, _KNM_CODE[K.fmt], K.n, K.M, _p(v1), _p(v2),
-                                                        _p(out1), _p(out2), _p(t_out), _p(ws), ws.numel(), self._stream()),
-                          "odx_knm_fwd_bwd2_q_t")
-            else:
-                hip.check(self.lib.odx_knm_fwd_bwd2_t(_p(K.K), K.ld, K.n, K.M, _p(v1), _p(v2), _p(out1), _p(out2), _p(t_out), _p(ws),
-                                                      ws.numel(), self._stream()), "odx_knm_fwd_bwd2_t")
-            return out1, out2
-        if K.fmt != "f32":
-            hip.check(self.lib.odx_knm_fwd_bwd2_q(_p(K.K), K.ld, _p(K.lo), K.ld, _KNM_CODE[K.fmt], K.n, K.M, _p(v1), _p(v2),
-                                                  _p(out1), _p(out2), _p(ws), ws.numel(), self._stream()), "odx_knm_fwd_bwd2_q")
-            return out1, out2
-        hip.check(self.lib.odx_knm_fwd_bwd2(_p(K.K), K.ld, K.n, K.M, _p(v1), _p(v2), _p(out1), _p(out2), _p(ws), ws.numel(),
-                                            self._stream()), "odx_knm_fwd_bwd2")
-        return out1, out2
 
     def cg_residual(self, B, AX, AP, state, R):
         """R = B - (AX + a AP), a = the step cg_step has just taken (state[3])."""
@@ -692,7 +584,7 @@ class HipBackend(PathOps):
         M = (ctypes.c_int64 * B)(*[int(v) for v in Ms])
         if fmt == "f32":
             return self.lib.odx_falkon_cg_batched_workspace_bytes(B, n, M) >= 0
-        return self.lib.odx_falkon_cg_batched_q_workspace_bytes(B, n, M, _KNM_CODE[fmt]) >= 0
+        return self.lib.odx_falkon_cg_batched_q_workspace_bytes(B, n, M, hip.KNM_CODE[fmt]) >= 0
 
     def cg_solve_batched(self, Ks, Ps, b0s, n_totals, lam, maxiter, opt):
         """The CG loops of len(Ks) <= 32 independent fits in lock step, one launch sequence for all of them
@@ -709,7 +601,7 @@ class HipBackend(PathOps):
         if fmt == "f32":
             nbytes = self.lib.odx_falkon_cg_batched_workspace_bytes(B, n, M)
         else:
-            nbytes = self.lib.odx_falkon_cg_batched_q_workspace_bytes(B, n, M, _KNM_CODE[fmt])
+            nbytes = self.lib.odx_falkon_cg_batched_q_workspace_bytes(B, n, M, hip.KNM_CODE[fmt])
         if nbytes < 0:
             return None
         base = Ps[0].LTi
@@ -725,7 +617,7 @@ class HipBackend(PathOps):
         ws = self._workspace("cg_solve_batched", nbytes)
         if fmt != "f32":
             lp = (ctypes.c_void_p * B)(*[(k.lo.data_ptr() if k.lo is not None else 0) for k in Ks])
-            hip.check(self.lib.odx_falkon_cg_batched_q_f64(B, kp, kl, lp, kl, _KNM_CODE[fmt], n, M, _p(base), ldp, p_rows, p_stride, _p(b0s),
+            hip.check(self.lib.odx_falkon_cg_batched_q_f64(B, kp, kl, lp, kl, hip.KNM_CODE[fmt], n, M, _p(base), ldp, p_rows, p_stride, _p(b0s),
                                                            b0s.stride(0), nt, float(lam), int(maxiter), int(opt.cg_full_gradient_every),
                                                            float(opt.cg_epsilon), float(opt.cg_tolerance), _p(alpha), _p(ws), ws.numel(),
                                                            self._stream()), "odx_falkon_cg_batched_q_f64")
@@ -761,30 +653,6 @@ class HipBackend(PathOps):
         hip.check(self.lib.odx_axpby_f64(float(a), _p(x), float(b), _p(y), y.numel(), self._stream()), "odx_axpby_f64")
 
     # ------------------------------------------------------------------ scoring
-    def knm_mv(self, K, alpha, out=None, summed=None):
-        """(n, 1) f32 = K alpha over a stored K_nM block, from one read of it (odx_knm_mv; f64 sums); `out` may be a
-        strided column such as scores[:, c:c + 1].  summed: the caller already holds K alpha as an (n,) f64 vector — the fit
-        that produced alpha summed it from its passes' row products (solver.falkon_fit(scores_out=...)) — and the block is
-        not read again: the sum is rounded once into `out` (odx_cg_scores_store_f32)."""
-        if K.fmt not in _KNM_CODE:
-            raise ValueError("knm_mv: needs a stored K_nM block, got %r (a streamed shard is scored by mmv)" % (K.fmt,))
-        if summed is not None:
-            if summed.numel() != K.n:
-                raise ValueError("knm_mv: summed has %d entries but the block has %d rows" % (summed.numel(), K.n))
-            if out is None:
-                out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
-            return self.cg_scores_store(summed, out)
-        alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
-        if alpha.numel() != K.M:
-            raise ValueError("knm_mv: alpha has %d entries but the block has %d columns" % (alpha.numel(), K.M))
-        if out is None:
-            out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
-        if out.dtype != torch.float32 or out.shape[0] != K.n or (out.dim() == 2 and out.shape[1] != 1):
-            raise ValueError("knm_mv: out must be an (n,) or (n, 1) f32 tensor")
-        hip.check(self.lib.odx_knm_mv(_p(K.K), K.ld, _p(K.lo), K.ld, _KNM_CODE[K.fmt], K.n, K.M, _p(alpha), _p(out),
-                                      out.stride(0), self._stream()), "odx_knm_mv")
-        return out
-
     def mmv(self, F, Zf, sigma, V, ranges=None, out=None, max_range=None):
         """(n, T) f32 = K(F, Zf) @ V with V (Mtot, T) f64; ``ranges`` (T, 2) int32 row ranges of the
         non-zero block of each column (None = dense); ``max_range``: an upper bound of the range lengths when the

@@ -14,6 +14,7 @@ _LIB_PATH = os.environ.get("ODX_LIB_PATH") or os.path.join(os.path.dirname(os.pa
 
 ODX_OK = 0
 KNM_F32, KNM_U24, KNM_BF16 = 0, 1, 2
+KNM_CODE = {"f32": KNM_F32, "u24": KNM_U24, "bf16": KNM_BF16}      # Knm.fmt -> the ODX_KNM_* code of include/odx.h
 STREAM_MAX_VECTORS = 16      # ODX_STREAM_MAX_VECTORS: vectors one odx_gauss_ktk_stream_h2n call serves from one build of K
 GEMM_LOWER_ONLY, GEMM_A_UPPER, GEMM_B_UPPER, GEMM_A_LOWER, GEMM_B_LOWER, GEMM_STORE_T = 1, 2, 4, 8, 16, 32
 

@@ -1,14 +1,20 @@
-"""Backend operations of fits that share one K_nM block: a lambda path (solver.falkon_fit_path: L penalties) and a
-multi-output fit (solver.falkon_fit_multi: T label columns, which share the preconditioner too).
+"""Backend operations over one K_nM block: the passes of the CG (``ktk``, ``ktk2``), the scoring pass (``knm_mv``) and what fits
+that share one block are driven by: a lambda path (solver.falkon_fit_path: L penalties) and a multi-output fit
+(solver.falkon_fit_multi: T label columns, which share the preconditioner too).
 
-``PathOps`` is mixed into ``backend.HipBackend``.  It adds the pass over several vectors from one read of the block
-(``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, the existing one- and two-vector passes for the rest; where the
-one-read pass does not exist — above M = 5084 — groups of up to 8 from TWO reads, ``kvn``: odx_knm_fwdn_q, then
-odx_knm_bwdn_q, when ``wide_pass_min`` is set; on a streamed shard odx_gauss_ktk_stream_h2n, up to 16 vectors from one BUILD
-of K), the preconditioners of a lambda path
-(``precond_path``: odx_falkon_precond_path_f64), the right-hand sides of several label columns from one read of the block
-(``ktwn``: odx_knm_bwdn_q) and the triangular products of several vectors from one read of a factor (``trmvn``:
-odx_trmvn_f64), all HIP through libodx.
+``PathOps`` is mixed into ``backend.HipBackend``.  It holds every wrapper of a pass over a stored block or a streamed shard,
+all HIP through libodx: one vector (``ktk``: odx_knm_fwd_bwd[_q]_t, odx_gauss_ktk_stream_h2), two (``ktk2``:
+odx_knm_fwd_bwd2[_q]_t), several from one read of the block (``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, ktk2 and
+ktk for the rest; where the one-read pass does not exist — above M = 5084 — groups of up to 8 from TWO reads, ``kvn``:
+odx_knm_fwdn_q, then odx_knm_bwdn_q, when ``wide_pass_min`` is set; on a streamed shard odx_gauss_ktk_stream_h2n, up to 16
+vectors from one BUILD of K), the right-hand sides of several label columns from one read of the block (``ktwn``:
+odx_knm_bwdn_q) and the scores K alpha (``knm_mv``: odx_knm_mv); beside them the preconditioners of a lambda path
+(``precond_path``: odx_falkon_precond_path_f64) and the triangular products of several vectors from one read of a factor
+(``trmvn``: odx_trmvn_f64).
+
+What every wrapper repeats is stated once, in the helpers below: the arguments a block is passed as (``_qblock``,
+``_fblock``), the workspace of an entry (``_pass_bytes``, ``_pass_ws``), the checks of a matrix of row vectors
+(``_check_matrix``, ``_check_aligned``), the groups of rows (``_groups``) and the call itself (``_call``).
 """
 import ctypes
 
@@ -16,20 +22,47 @@ import torch
 
 from . import hip
 
-_CODE = {"u24": hip.KNM_U24, "bf16": hip.KNM_BF16}
-
 
 def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-def _aligned_rows(*ts):
-    return all(t.stride(0) % 2 == 0 and t.data_ptr() % 16 == 0 for t in ts)
+def _compact(K):
+    """Whether K is a stored block in a compact format (u24 / bf16): what the _q entries take."""
+    return K.fmt in hip.KNM_CODE and K.fmt != "f32"
+
+
+def _qblock(K):
+    """The five arguments a compact-format entry (and odx_knm_mv, for every stored format) takes a block as."""
+    return _p(K.K), K.ld, _p(K.lo), K.ld, hip.KNM_CODE[K.fmt]
+
+
+def _fblock(K):
+    """The two arguments an f32 entry takes a block as."""
+    return _p(K.K), K.ld
+
+
+def _groups(L, width):
+    """(first, count) of the groups of up to `width` consecutive rows of L."""
+    for l in range(0, L, width):
+        yield l, min(width, L - l)
+
+
+def _check_matrix(who, name, t, rows, cols):
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or t.dtype != torch.float64 or t.stride(1) != 1:
+        raise ValueError("%s: %s must be a (%d, >= %d) f64 matrix with contiguous rows" % (who, name, rows, cols))
+
+
+def _check_aligned(who, **ts):
+    """Every row of the matrices starts on 16 bytes (an aligned first row and an even leading dimension)."""
+    if not all(t.stride(0) % 2 == 0 and t.data_ptr() % 16 == 0 for t in ts.values()):
+        raise ValueError("%s: rows of %s must be 16-byte aligned (even leading dimension)" % (who, " and ".join(ts)))
 
 
 class PathOps:
-    """ktkn / ktkn_width / ktkn_span / kvn / precond_path of HipBackend.  On a streamed shard (KnmStream) ktkn makes ONE build
-    of K per group of ktkn_span = 16 vectors; ktkn_width keeps meaning vectors per READ of the block or ring (2 there)."""
+    """The passes over a K_nM block of HipBackend (ktk / ktk2 / ktkn / kvn / ktwn / knm_mv), trmvn and precond_path.  On a
+    streamed shard (KnmStream) ktkn makes ONE build of K per group of ktkn_span = 16 vectors; ktkn_width keeps meaning vectors
+    per READ of the block or ring (2 there)."""
 
     # The smallest group of vectors that ktkn sends through the two-read route (odx_knm_fwdn_q + odx_knm_bwdn_q, up to 8
     # vectors per two reads) on a compact block whose one-read width is 2 or 1; None: never (pairs and singles as before).
@@ -38,14 +71,100 @@ class PathOps:
     wide_pass_min = None
     WIDE_PASS_MAX = 8           # vectors per call of odx_knm_fwdn_q / odx_knm_bwdn_q
 
+    # ------------------------------------------------------------------ plumbing
+    def _call(self, entry, *args):
+        hip.check(getattr(self.lib, entry)(*args, self._stream()), entry)
+
+    def _pass_bytes(self, entry, n, M, *more):
+        """What <entry>_workspace_bytes(n, M, *more) says; OdxError where the entry has no kernel for M."""
+        nbytes = int(getattr(self.lib, entry + "_workspace_bytes")(n, M, *more))
+        if nbytes < 0:
+            raise hip.OdxError("%s: M = %d is outside the supported range" % (entry, M))
+        return nbytes
+
+    def _pass_ws(self, key, entry, K, *more):
+        """The workspace `key`, large enough for `entry` over the block K."""
+        return self._workspace(key, self._pass_bytes(entry, max(K.n, 1), K.M, *more))
+
+    def _stream_bytes(self, n, M, D):
+        return self._pass_bytes("odx_gauss_ktk_stream_h2", n, M, D)
+
+    # ------------------------------------------------------------------ one and two vectors
+    def _ktk_stream(self, K, v, v2, w, out, out2):
+        """out = K' (K v + w) [, out2 = K' (K v2)] with K recomputed chunk by chunk (odx_gauss_ktk_stream_h2)."""
+        F, Zf = K.F, K.Zf
+        nbytes = self._stream_bytes(max(K.n, 1), K.M, F.D)
+        ws = K.ring if K.ring is not None else self._workspace("ktk_stream", nbytes)
+        self._call("odx_gauss_ktk_stream_h2", _p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), K.n, _p(Zf.P), Zf.P.stride(0), _p(Zf.meta),
+                   _p(Zf.sq), K.M, F.D, K.sigma, _p(v), _p(v2), _p(w), _p(out), _p(out2), _p(ws), ws.numel())
+
+    def _check_t_out(self, K, v, t_out):
+        if K.fmt == "stream":
+            raise ValueError("ktk: t_out needs a stored K_nM block (a streamed shard's rows pass in chunks)")
+        if v is None:
+            raise ValueError("ktk: t_out is the row product K v: it needs v")
+        if t_out.dtype != torch.float64 or t_out.numel() != K.n or not t_out.is_contiguous():
+            raise ValueError("ktk: t_out must be a contiguous f64 vector of the block's %d rows" % K.n)
+
+    def ktk(self, K, v=None, w=None, out=None, t_out=None):
+        """out = K' (K v + w) over this shard (f64).  t_out: optional (n,) f64 that receives the row products K v (before w
+        is added), a by-product of the same read of K (odx_knm_fwd_bwd[_q]_t); `out` is bitwise the same with or without it."""
+        if out is None:
+            out = torch.empty(K.M, dtype=torch.float64, device=self.device)
+        if t_out is not None:
+            self._check_t_out(K, v, t_out)
+        if K.fmt == "stream":
+            self._ktk_stream(K, v, None, w, out, None)
+            return out
+        # (the _t entries with a null t_out ARE the plain entries: one function in C)
+        if _compact(K):
+            ws = self._pass_ws("ktk", "odx_knm_fwd_bwd_q", K, hip.KNM_CODE[K.fmt])
+            self._call("odx_knm_fwd_bwd_q_t", *_qblock(K), K.n, K.M, _p(v), _p(w), _p(out), _p(t_out), _p(ws), ws.numel())
+        else:
+            ws = self._pass_ws("ktk", "odx_knm_fwd_bwd", K)
+            self._call("odx_knm_fwd_bwd_t", *_fblock(K), K.n, K.M, _p(v), _p(w), _p(out), _p(t_out), _p(ws), ws.numel())
+        return out
+
+    def _ktk2_bytes(self, K):
+        if _compact(K):
+            return self.lib.odx_knm_fwd_bwd2_q_workspace_bytes(max(K.n, 1), K.M, hip.KNM_CODE[K.fmt])
+        return self.lib.odx_knm_fwd_bwd2_workspace_bytes(max(K.n, 1), K.M)
+
+    def can_ktk2(self, K):
+        """Whether the two-vector pass exists at this block's width (both vectors must fit in LDS: M <= 10 000).  A streamed
+        shard always has one: each chunk is built once and read for both vectors while it is resident."""
+        return K.fmt == "stream" or self._ktk2_bytes(K) >= 0
+
+    def ktk2(self, K, v1, v2, out1=None, out2=None, t_out=None):
+        """out1 = K' (K v1), out2 = K' (K v2) over this shard from ONE read of K (odx_knm_fwd_bwd2[_q]).  t_out: optional
+        (n,) f64 that receives the row products K v1 (odx_knm_fwd_bwd2[_q]_t)."""
+        if t_out is not None:
+            self._check_t_out(K, v1, t_out)
+        if out1 is None:
+            out1 = torch.empty(K.M, dtype=torch.float64, device=self.device)
+        if out2 is None:
+            out2 = torch.empty(K.M, dtype=torch.float64, device=self.device)
+        if K.fmt == "stream":
+            self._ktk_stream(K, v1, v2, None, out1, out2)
+            return out1, out2
+        vecs = (_p(v1), _p(v2), _p(out1), _p(out2), _p(t_out))
+        if _compact(K):
+            ws = self._pass_ws("ktk", "odx_knm_fwd_bwd2_q", K, hip.KNM_CODE[K.fmt])
+            self._call("odx_knm_fwd_bwd2_q_t", *_qblock(K), K.n, K.M, *vecs, _p(ws), ws.numel())
+        else:
+            ws = self._pass_ws("ktk", "odx_knm_fwd_bwd2", K)
+            self._call("odx_knm_fwd_bwd2_t", *_fblock(K), K.n, K.M, *vecs, _p(ws), ws.numel())
+        return out1, out2
+
+    # ------------------------------------------------------------------ several vectors
     def _ktkn_bytes(self, K, nv):
-        return self.lib.odx_knm_fwd_bwdn_q_workspace_bytes(max(K.n, 1), K.M, _CODE[K.fmt], nv)
+        return self.lib.odx_knm_fwd_bwdn_q_workspace_bytes(max(K.n, 1), K.M, hip.KNM_CODE[K.fmt], nv)
 
     def ktkn_width(self, K):
         """The largest number of vectors ONE read of K serves: 8 or 4 where the NV-vector pass over a compact block has a
         configuration (the vectors sit in LDS as f64: 8 up to M = 2524, 4 up to M = 5084), else 2 where the two-vector pass
         exists, else 1.  f32 blocks (small, not HBM-bound) and streamed shards are served by ktk / ktk2 only."""
-        if K.fmt in _CODE:
+        if _compact(K):
             for nv in (8, 4):
                 if self._ktkn_bytes(K, nv) >= 0:
                     return nv
@@ -61,13 +180,10 @@ class PathOps:
         """Rows [l, l + g) of V through one build of the streamed shard (odx_gauss_ktk_stream_h2n).  The ring: the caller's
         buffer when it is large enough for this entry (a buffer sized for ktk / ktk2 may not be), else the backend's."""
         F, Zf = K.F, K.Zf
-        nbytes = int(self.lib.odx_gauss_ktk_stream_h2n_workspace_bytes(max(K.n, 1), K.M, F.D, g))
-        if nbytes < 0:
-            raise hip.OdxError("odx_gauss_ktk_stream_h2n: M = %d is outside the supported range (M <= 20440)" % K.M)
+        nbytes = self._pass_bytes("odx_gauss_ktk_stream_h2n", max(K.n, 1), K.M, F.D, g)
         ws = K.ring if K.ring is not None and K.ring.numel() >= nbytes else self._workspace("ktkn_stream", nbytes)
-        hip.check(self.lib.odx_gauss_ktk_stream_h2n(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), K.n, _p(Zf.P), Zf.P.stride(0),
-                                                    _p(Zf.meta), _p(Zf.sq), K.M, F.D, K.sigma, g, _p(V[l]), V.stride(0), _p(out[l]),
-                                                    out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_ktk_stream_h2n")
+        self._call("odx_gauss_ktk_stream_h2n", _p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), K.n, _p(Zf.P), Zf.P.stride(0), _p(Zf.meta),
+                   _p(Zf.sq), K.M, F.D, K.sigma, g, _p(V[l]), V.stride(0), _p(out[l]), out.stride(0), _p(ws), ws.numel())
 
     def _ktkn_plan(self, K, L):
         """The calls ktkn makes for L vectors over a stored block, in order: (kind, first vector, count) with kind "nv"
@@ -76,7 +192,7 @@ class PathOps:
         width = self.ktkn_width(K)
         plan, l = [], 0
         wmin = self.wide_pass_min
-        if wmin is not None and width <= 2 and K.fmt in _CODE:
+        if wmin is not None and width <= 2 and _compact(K):
             while L - l >= max(int(wmin), 1):
                 g = min(self.WIDE_PASS_MAX, L - l)
                 plan.append(("wide", l, g))
@@ -94,44 +210,37 @@ class PathOps:
             return -(-L // self.ktkn_span(K))
         return sum({"nv": 1, "wide": 2, "pair": 1, "single": g}[kind] for kind, _, g in self._ktkn_plan(K, L))
 
+    def _nv_call(self, entry, key, K, g, A, B):
+        """One of the three NV-vector entries over a compact block: g rows from A[0] on in, g rows from B[0] on out, its
+        slabs in the workspace `key` (None: the entry needs none and is only asked whether it serves M)."""
+        nbytes = self._pass_bytes(entry, max(K.n, 1), K.M, hip.KNM_CODE[K.fmt], g)
+        ws = self._workspace(key, nbytes) if key else None
+        self._call(entry, *_qblock(K), K.n, K.M, g, _p(A[0]), A.stride(0), _p(B[0]), B.stride(0), _p(ws), ws.numel() if key else 0)
+
     def kvn(self, K, V, out=None):
         """out[l] = K V[l] (the row products, f64) for the L >= 1 rows of V ((L, >= M) f64) over a compact stored block: groups
         of up to 8 rows from ONE read each (odx_knm_fwdn_q, every M <= 20440).  out: (L, >= roundup(n, 2)) f64; cells [n:]
         of a row are not written.  Rows of V and out must be 16-byte aligned.  f32 blocks and streamed shards: ValueError
         (the entry is not built for them)."""
-        if K.fmt not in _CODE:
+        if not _compact(K):
             raise ValueError("kvn: compact stored blocks only (u24 / bf16), got %r" % (K.fmt,))
         L, M, n = V.shape[0], K.M, K.n
         if out is None:
             out = torch.zeros((L, (n + 1) // 2 * 2), dtype=torch.float64, device=self.device)
-        for t, cols in ((V, M), (out, n)):
-            if t.dim() != 2 or t.shape[0] != L or t.shape[1] < cols or t.dtype != torch.float64 or t.stride(1) != 1:
-                raise ValueError("kvn: V must be a (L, >= M) and out a (L, >= n) f64 matrix with contiguous rows")
-        if not _aligned_rows(V, out):
-            raise ValueError("kvn: rows of V and out must be 16-byte aligned (even leading dimension)")
-        for l in range(0, L if n > 0 else 0, self.WIDE_PASS_MAX):
-            g = min(self.WIDE_PASS_MAX, L - l)
-            if self.lib.odx_knm_fwdn_q_workspace_bytes(max(n, 1), M, _CODE[K.fmt], g) < 0:
-                raise hip.OdxError("odx_knm_fwdn_q: M = %d is outside the supported range (M <= 20440)" % M)
-            hip.check(self.lib.odx_knm_fwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], n, M, g,
-                                              _p(V[l]), V.stride(0), _p(out[l]), out.stride(0), None, 0, self._stream()),
-                      "odx_knm_fwdn_q")
+        _check_matrix("kvn", "V", V, L, M)
+        _check_matrix("kvn", "out", out, L, n)
+        _check_aligned("kvn", V=V, out=out)
+        for l, g in _groups(L if n > 0 else 0, self.WIDE_PASS_MAX):
+            self._nv_call("odx_knm_fwdn_q", None, K, g, V[l:], out[l:])
         return out
 
     def _ktkn_wide(self, K, V, out, l, g):
         """Rows [l, l + g) of V, g <= 8, from two reads of the block: T = K V (odx_knm_fwdn_q), out = K' T (odx_knm_bwdn_q).
         T has a workspace of its own: "ktk" holds the backward kernel's slabs."""
-        n, M = K.n, K.M
-        ldt = (max(n, 1) + 1) // 2 * 2
+        ldt = (max(K.n, 1) + 1) // 2 * 2
         T = self._workspace("ktkn_t", g * ldt * 8)[:g * ldt * 8].view(torch.float64).view(g, ldt)
         self.kvn(K, V[l:l + g], out=T)
-        nbytes = self.lib.odx_knm_bwdn_q_workspace_bytes(max(n, 1), M, _CODE[K.fmt], g)
-        if nbytes < 0:
-            raise hip.OdxError("odx_knm_bwdn_q: M = %d is outside the supported range (M <= 20440)" % M)
-        ws = self._workspace("ktk", nbytes)
-        hip.check(self.lib.odx_knm_bwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], n, M, g,
-                                          _p(T), ldt, _p(out[l]), out.stride(0), _p(ws), ws.numel(), self._stream()),
-                  "odx_knm_bwdn_q")
+        self._nv_call("odx_knm_bwdn_q", "ktk", K, g, T, out[l:])
 
     def ktkn(self, K, V, out=None):
         """out[l] = K' (K V[l]) for the L >= 1 rows of V ((L, ld) f64), with as few reads of K as its width allows: groups of
@@ -145,31 +254,23 @@ class PathOps:
         L, M = V.shape[0], K.M
         if out is None:
             out = torch.zeros((L, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
-        for t in (V, out):
-            if t.dim() != 2 or t.shape[0] != L or t.shape[1] < M or t.dtype != torch.float64 or t.stride(1) != 1:
-                raise ValueError("ktkn: V and out must be (L, >= M) f64 matrices with contiguous rows")
+        _check_matrix("ktkn", "V", V, L, M)
+        _check_matrix("ktkn", "out", out, L, M)
         if K.fmt == "stream":
-            span = self.ktkn_span(K)
-            for l in range(0, L, span):
-                g = min(span, L - l)
+            for l, g in _groups(L, self.ktkn_span(K)):
                 if g == 1:
                     self.ktk(K, v=V[l, :M], out=out[l, :M])
                     continue
-                if V.stride(0) % 2 or out.stride(0) % 2 or V[l].data_ptr() % 16 or out[l].data_ptr() % 16:
-                    raise ValueError("ktkn: rows of V and out must be 16-byte aligned (even leading dimension)")
+                _check_aligned("ktkn", V=V, out=out)
                 self._ktkn_stream(K, V, out, l, g)
             return out
         for kind, l, g in self._ktkn_plan(K, L):
             if kind in ("nv", "wide"):
-                if V.stride(0) % 2 or out.stride(0) % 2 or V[l].data_ptr() % 16 or out[l].data_ptr() % 16:
-                    raise ValueError("ktkn: rows of V and out must be 16-byte aligned (even leading dimension)")
+                _check_aligned("ktkn", V=V, out=out)
             if kind == "wide":
                 self._ktkn_wide(K, V, out, l, g)
             elif kind == "nv":
-                ws = self._workspace("ktk", self._ktkn_bytes(K, g))
-                hip.check(self.lib.odx_knm_fwd_bwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], K.n, M, g,
-                                                      _p(V[l]), V.stride(0), _p(out[l]), out.stride(0), _p(ws), ws.numel(),
-                                                      self._stream()), "odx_knm_fwd_bwdn_q")
+                self._nv_call("odx_knm_fwd_bwdn_q", "ktk", K, g, V[l:], out[l:])
             elif kind == "pair":
                 self.ktk2(K, V[l, :M], V[l + 1, :M], out1=out[l, :M], out2=out[l + 1, :M])
             else:
@@ -186,23 +287,14 @@ class PathOps:
         T, M, n = W.shape[0], K.M, K.n
         if out is None:
             out = torch.zeros((T, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
-        for t, cols in ((W, n), (out, M)):
-            if t.dim() != 2 or t.shape[0] != T or t.shape[1] < cols or t.dtype != torch.float64 or t.stride(1) != 1:
-                raise ValueError("ktwn: W must be a (T, >= n) and out a (T, >= M) f64 matrix with contiguous rows")
-        for l in range(0, T, 8 if K.fmt in _CODE else 1):
-            g = min(8, T - l) if K.fmt in _CODE else 1
+        _check_matrix("ktwn", "W", W, T, n)
+        _check_matrix("ktwn", "out", out, T, M)
+        for l, g in _groups(T, self.WIDE_PASS_MAX if _compact(K) else 1):
             if g == 1:
                 self.ktk(K, w=W[l, :n], out=out[l, :M])
                 continue
-            if W.stride(0) % 2 or out.stride(0) % 2 or W[l].data_ptr() % 16 or out[l].data_ptr() % 16:
-                raise ValueError("ktwn: rows of W and out must be 16-byte aligned (even leading dimension)")
-            nbytes = self.lib.odx_knm_bwdn_q_workspace_bytes(max(n, 1), M, _CODE[K.fmt], g)
-            if nbytes < 0:
-                raise hip.OdxError("odx_knm_bwdn_q: M = %d is outside the supported range (M <= 20440)" % M)
-            ws = self._workspace("ktk", nbytes)
-            hip.check(self.lib.odx_knm_bwdn_q(_p(K.K), K.ld, _p(K.lo) if K.lo is not None else None, K.ld, _CODE[K.fmt], n, M, g,
-                                              _p(W[l]), W.stride(0), _p(out[l]), out.stride(0), _p(ws), ws.numel(), self._stream()),
-                      "odx_knm_bwdn_q")
+            _check_aligned("ktwn", W=W, out=out)
+            self._nv_call("odx_knm_bwdn_q", "ktk", K, g, W[l:], out[l:])
         return out
 
     def trmvn(self, P, name, X, alpha=1.0, beta=0.0, Z=None, out=None):
@@ -211,21 +303,41 @@ class PathOps:
         T, M = X.shape[0], P.M
         if out is None:
             out = torch.zeros((T, P.ld), dtype=torch.float64, device=self.device)
-        for t in (X, out) + (() if Z is None else (Z,)):
-            if t.dim() != 2 or t.shape[0] != T or t.shape[1] < M or t.dtype != torch.float64 or t.stride(1) != 1:
-                raise ValueError("trmvn: X, Z and out must be (T, >= M) f64 matrices with contiguous rows")
+        for nm, t in (("X", X), ("out", out)) + (() if Z is None else (("Z", Z),)):
+            _check_matrix("trmvn", nm, t, T, M)
         if beta != 0.0 and Z is None:
             raise ValueError("trmvn: beta needs Z")
-        for l in range(0, T, 8):
-            g = min(8, T - l)
+        for l, g in _groups(T, 8):
             if g == 1:
                 self.trmv(P, name, X[l], alpha=alpha, beta=beta, z=None if Z is None else Z[l], out=out[l])
                 continue
-            if X.stride(0) % 2 or X[l].data_ptr() % 16:
-                raise ValueError("trmvn: rows of X must be 16-byte aligned (even leading dimension)")
-            hip.check(self.lib.odx_trmvn_f64(_p(getattr(P, name)), P.ld, M, self._TRI[name], g, _p(X[l]), X.stride(0), float(alpha),
-                                             float(beta), None if Z is None else _p(Z[l]), 0 if Z is None else Z.stride(0), _p(out[l]),
-                                             out.stride(0), self._stream()), "odx_trmvn_f64")
+            _check_aligned("trmvn", X=X)
+            self._call("odx_trmvn_f64", _p(getattr(P, name)), P.ld, M, self._TRI[name], g, _p(X[l]), X.stride(0), float(alpha),
+                       float(beta), _p(None if Z is None else Z[l]), 0 if Z is None else Z.stride(0), _p(out[l]), out.stride(0))
+        return out
+
+    # ------------------------------------------------------------------ scoring
+    def knm_mv(self, K, alpha, out=None, summed=None):
+        """(n, 1) f32 = K alpha over a stored K_nM block, from one read of it (odx_knm_mv; f64 sums); `out` may be a
+        strided column such as scores[:, c:c + 1].  summed: the caller already holds K alpha as an (n,) f64 vector — the fit
+        that produced alpha summed it from its passes' row products (solver.falkon_fit(scores_out=...)) — and the block is
+        not read again: the sum is rounded once into `out` (odx_cg_scores_store_f32)."""
+        if K.fmt not in hip.KNM_CODE:
+            raise ValueError("knm_mv: needs a stored K_nM block, got %r (a streamed shard is scored by mmv)" % (K.fmt,))
+        if summed is not None:
+            if summed.numel() != K.n:
+                raise ValueError("knm_mv: summed has %d entries but the block has %d rows" % (summed.numel(), K.n))
+            if out is None:
+                out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
+            return self.cg_scores_store(summed, out)
+        alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
+        if alpha.numel() != K.M:
+            raise ValueError("knm_mv: alpha has %d entries but the block has %d columns" % (alpha.numel(), K.M))
+        if out is None:
+            out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or out.shape[0] != K.n or (out.dim() == 2 and out.shape[1] != 1):
+            raise ValueError("knm_mv: out must be an (n,) or (n, 1) f32 tensor")
+        self._call("odx_knm_mv", *_qblock(K), K.n, K.M, _p(alpha), _p(out), out.stride(0))
         return out
 
     def precond_path(self, Zf, sigma, lams, eps, out=None, ws_key="precond"):
