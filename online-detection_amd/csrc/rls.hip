@@ -255,15 +255,16 @@ __global__ __launch_bounds__(256, 3) void rls_gram_rows32_kernel(const float* __
       float* db = lds_b + (krow + 16 * h) * RG32_LDB + seg * 2;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float m = valid[h] && aok[q] ? 1.f : 0.f;
-        *reinterpret_cast<f32x2r*>(da + q * 32) = f32x2r{m * ra[h][q][0], m * ra[h][q][1]};
+        const bool ok = valid[h] && aok[q];                    // (selected, not multiplied by 0: the stand-in operand may be Inf / NaN)
+        *reinterpret_cast<f32x2r*>(da + q * 32) = f32x2r{ok ? ra[h][q][0] : 0.f, ok ? ra[h][q][1] : 0.f};
       }
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        const float m = valid[h] && bok[q] ? 1.f : 0.f;
-        *reinterpret_cast<f32x2r*>(db + q * 32) = f32x2r{m * rb[h][q][0], m * rb[h][q][1]};
+        const bool ok = valid[h] && bok[q];
+        *reinterpret_cast<f32x2r*>(db + q * 32) = f32x2r{ok ? rb[h][q][0] : 0.f, ok ? rb[h][q][1] : 0.f};
       }
-      if (xty && seg == 0) *reinterpret_cast<f32x4r*>(lds_y + (krow + 16 * h) * 4) = ry[h];   // (a padded row's A entries are zero)
+      if (xty && seg == 0)                                     // (a padded row's targets are zero like its A entries: 0 x NaN is NaN)
+        *reinterpret_cast<f32x4r*>(lds_y + (krow + 16 * h) * 4) = valid[h] ? ry[h] : f32x4r{0.f, 0.f, 0.f, 0.f};
     }
     __syncthreads();
     load(row_next[0], 0);
