@@ -167,6 +167,16 @@ int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax, const flo
                      const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D,
                      double sigma, const double* V, int64_t ldv, const int32_t* ranges, int T,
                      float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* Scoring with a DENSE V whose T columns all weigh the same M centres (a multi-output model, the members of a lambda
+ * path): every entry of K(X, Z) is evaluated once per group of up to 8 columns instead of once per column.  out (n, T) is
+ * bit for bit what odx_gauss_mmv_h2 gives for the same V with every range [0, M) and max_range = M (same tile core, same
+ * groups, same f64 sums per column).  V needs 8-byte alignment and ldv >= T only.  Workspace: the same number of bytes as
+ * odx_gauss_mmv_h2_workspace_bytes(n, M, T).  n <= 0 or T <= 0: ODX_OK, nothing written. */
+int64_t odx_gauss_mmvn_h2_workspace_bytes(int64_t n, int64_t M, int T);
+int odx_gauss_mmvn_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                      const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                      double sigma, const double* V, int64_t ldv, int T,
+                      float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 /* ---------------------------------------------------------------- A4: CG pass on stored K
  * falkon's incore_fdmmv on the stored K_nM (selected by store_kernel_d_threshold=250,

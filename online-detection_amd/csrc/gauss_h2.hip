@@ -521,6 +521,130 @@ __global__ __launch_bounds__(256) void mmv_reduce_kernel(const double* __restric
   out[row * ldo + c] = (float)s;
 }
 
+// The entries of a tile are read once per column of the group; without this the compiler converts all of them to f64 ONCE
+// and keeps the doubles (twice the accumulators' registers: scratch).  No instruction: the values just become opaque.
+template <int TM>
+__device__ __forceinline__ void mmvn_fresh(f32x4 (&acc)[TM][4]) {
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) {        // (component by component: as whole 4-register tuples they cost the wide kernels scratch)
+      float e0 = acc[tm][tn][0], e1 = acc[tm][tn][1], e2 = acc[tm][tn][2], e3 = acc[tm][tn][3];
+      asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3));
+      acc[tm][tn][0] = e0, acc[tm][tn][1] = e1, acc[tm][tn][2] = e2, acc[tm][tn][3] = e3;
+    }
+}
+
+// Shared-centre form of gauss_mmv_h2s16_kernel for a DENSE V (every column weighs all M centres): blockIdx.y is a group of
+// up to NV columns c0 .. c0 + NV - 1 of V, and a tile's entries exp2(.) are formed ONCE — written over the accumulators —
+// and then weighed by one column after the other.  Per column the f64 operations and their order (the fma chain over tn,
+// the butterflies, the sum over the tiles, the two halves in `red`, the slab) are those of gauss_mmv_h2s16_kernel with the
+// range [0, M): the same bits.  Columns past T (the padding of a group narrower than NV) weigh 0 and are not stored.
+template <int NV>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
+    const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
+    const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
+    int ktiles, float gamma_log2e, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
+    double* __restrict__ slab, int64_t slab_ld) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ __attribute__((aligned(16))) float xg_s[GEMM_BM];      // row norms times gamma log2(e)
+  constexpr int64_t GR = 8;
+  const int c0 = cbase + (int)blockIdx.y * NV;
+  const int nc = T - c0 < NV ? T - c0 : NV;
+  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t band = wg / (GR * G), within = wg % (GR * G);
+  const int64_t i0 = (band * GR + within % GR) * GEMM_BM;
+  const int g = (int)(within / GR);
+  const int64_t s0 = (int64_t)g * tg * GEMM_BN;
+  const int64_t s1 = (s0 + (int64_t)tg * GEMM_BN < M) ? s0 + (int64_t)tg * GEMM_BN : M;
+  if (i0 >= n || s0 >= M) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const float m2g = -2.f / (metax[0] * metaz[0]) * gamma_log2e;
+
+  if (threadIdx.x < GEMM_BM) xg_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] * gamma_log2e : 0.f;
+  double tot[NV];
+#pragma unroll
+  for (int c = 0; c < NV; ++c) tot[c] = 0.0;
+  const bool b8 = lane & 8, b4 = lane & 4, b2 = lane & 2, b1 = lane & 1;
+
+  for (int64_t j0 = s0; j0 < s1; j0 += GEMM_BN) {
+    f32x4 acc[4][4];
+    s16_zero(acc);
+    s16_mainloop(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, ktiles, lds);
+    float zs[4];
+    int64_t voff[4];                    // < 0: a column past the group / M (weight 0)
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) {
+      const int64_t col = j0 + wc * 64 + tn * 16 + (lane & 15);
+      const bool cv = col < s1;
+      zs[tn] = cv ? zsq[col] * gamma_log2e : 0.f;
+      voff[tn] = cv ? col * ldv + c0 : -1;
+    }
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float xs = xg_s[wr * 64 + tm * 16 + 4 * (lane >> 4) + q];
+#pragma unroll
+        for (int tn = 0; tn < 4; ++tn)      // gamma < 0: d^2 >= 0 <=> e <= 0
+          acc[tm][tn][q] = __builtin_amdgcn_exp2f(fminf(fmaf(m2g, acc[tm][tn][q], xs) + zs[tn], 0.f));
+      }
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      mmvn_fresh(acc);
+      double al[4];
+#pragma unroll
+      for (int tn = 0; tn < 4; ++tn) al[tn] = (voff[tn] >= 0 && c < nc) ? V[voff[tn] + c] : 0.0;
+      double w8[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {       // slots j (tm = j >> 2) and j + 8 (tm = 2 + (j >> 2)), q = j & 3
+        double v[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int tm = 2 * u + (j >> 2), q = j & 3;
+          v[u] = 0.0;
+#pragma unroll
+          for (int tn = 0; tn < 4; ++tn) v[u] = fma((double)acc[tm][tn][q], al[tn], v[u]);
+        }
+        w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+      }
+      double w4[4], w2[2];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
+      tot[c] += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+    }
+  }
+  __syncthreads();                            // every wave is done with the operand images: `red` takes their place
+  double* red = reinterpret_cast<double*>(lds);       // [NV][2 (wr)][2 (wc)][64]
+  {
+    const int slot = lane & 15;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) red[((c * 2 + wr) * 2 + wc) * 64 + (slot >> 2) * 16 + 4 * (lane >> 4) + (slot & 3)] = tot[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int w = threadIdx.x >> 6, rr = threadIdx.x & 63;
+    const int64_t row = i0 + w * 64 + rr;
+    if (row < n)
+      for (int c = 0; c < nc; ++c)
+        slab[((int64_t)(c0 + c) * G + g) * slab_ld + row] = red[((c * 2 + w) * 2 + 0) * 64 + rr] + red[((c * 2 + w) * 2 + 1) * 64 + rr];
+  }
+}
+
+// mmv_reduce_kernel for a dense V: every column has all G groups.
+__global__ __launch_bounds__(256) void mmvn_reduce_kernel(const double* __restrict__ slab, int64_t slab_ld, int G, int64_t n,
+                                                          float* __restrict__ out, int64_t ldo) {
+  const int c = blockIdx.y;
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  double s = 0.0;
+  for (int g = 0; g < G; ++g) s += slab[((int64_t)c * G + g) * slab_ld + row];
+  out[row * ldo + c] = (float)s;
+}
+
 // ---------------------------------------------------------------- 256 x 256 tile core ("w256")
 // 512 threads = 8 waves as 2 (rows) x 4 (columns); a wave owns 128 x 64 outputs = 8 x 4 blocks of v_mfma_f32_16x16x32_f16
 // (128 accumulator registers).  A k-stage is one granule (32 features = 128 B) of 256 rows of each operand: 64 KiB, held
@@ -1744,6 +1868,126 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmv_h2w256_kernel(
   }
 }
 
+// Shared-centre form of gauss_mmv_h2w256_kernel (see gauss_mmvn_h2s16_kernel): the entries of a tile replace its
+// accumulators, then today's weighted sum and butterflies run once per column of the group.  Same f64 operations in the
+// same order per column as gauss_mmv_h2w256_kernel with the range [0, M).  The accumulators stay live through all NV
+// columns (there they die as they are read), so the column sums are kept out of the registers: see `park` and `mine`.
+template <int NV, int CORE>
+__global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_h2w256_kernel(
+    const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
+    const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
+    int stages, float gamma_log2e, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
+    double* __restrict__ slab, int64_t slab_ld) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ __attribute__((aligned(16))) float xs_s[W_BM];
+  // The sums of the first PARK columns stay in LDS of their own for the whole kernel: 3 x 8 KiB is what the CU has left
+  // beside the operand images, and the 4 NV registers of all NV sums do not fit beside the main loop's at NV = 8.
+  constexpr int PARK = NV < 3 ? NV : 3;
+  __shared__ double park[PARK][4][W_BM];
+  constexpr int64_t GR = 8;
+  const int c0 = cbase + (int)blockIdx.y * NV;
+  const int nc = T - c0 < NV ? T - c0 : NV;
+  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t band = wg / (GR * G), within = wg % (GR * G);
+  const int64_t i0 = (band * GR + within % GR) * W_BM;
+  const int g = (int)(within / GR);
+  const int64_t s0 = (int64_t)g * tg * W_BN;
+  const int64_t s1 = (s0 + (int64_t)tg * W_BN < M) ? s0 + (int64_t)tg * W_BN : M;
+  if (i0 >= n || s0 >= M) return;
+  const float m2 = -2.f / (metax[0] * metaz[0]);
+  double* red = reinterpret_cast<double*>(lds);       // [NV][4 (wc)][W_BM], over the operand images (w_mainloop_dma ends on a barrier)
+
+  if (threadIdx.x < W_BM) xs_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] : 0.f;
+  double tot[NV - PARK + 1][2];           // (+ 1: no empty array at NV = 2)
+#pragma unroll
+  for (int c = 0; c < NV - PARK; ++c) tot[c][0] = tot[c][1] = 0.0;
+  {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* mine = &park[0][wave & 3][(wave >> 2) * 128 + 16 * ((lane & 15) >> 2) + 4 * (lane >> 4) + (lane & 3)];
+#pragma unroll
+    for (int c = 0; c < PARK; ++c) mine[c * 4 * W_BM] = mine[c * 4 * W_BM + 64] = 0.0;
+  }
+
+  for (int64_t j0 = s0; j0 < s1; j0 += W_BN) {
+    f32x4 acc[8][4];
+    w_zero(acc);
+    w_mainloop_dma<false, CORE>(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, stages, lds);
+    // The lane's place in the tile is derived HERE, from a thread index the compiler cannot see through: computed at kernel
+    // entry, the offsets and masks below are live across the main loop beside 2 NV sums, and that is more than 256 registers.
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wr = tid >> 8, wc = (tid >> 6) & 3;
+    const bool b8 = lane & 8, b4 = lane & 4, b2 = lane & 2, b1 = lane & 1;
+    // During the epilogue the other sums live in this lane's own slots of `red` (the operand images are free until the next
+    // main loop starts), not in registers beside the accumulators; they are registers only ACROSS a main loop.
+    const int slot = wc * W_BM + wr * 128 + 16 * ((lane & 15) >> 2) + 4 * (lane >> 4) + (lane & 3);
+    double* mine = red + slot;
+    double* parked = &park[0][0][0] + slot;
+#pragma unroll
+    for (int c = 0; c < NV - PARK; ++c) mine[c * 4 * W_BM] = tot[c][0], mine[c * 4 * W_BM + 64] = tot[c][1];
+    float zs[4];
+    const int64_t col0 = j0 + wc * 64 + (lane & 15);       // this lane's columns: col0 + 16 tn; past the group / M: weight 0
+    const double* vp = V + col0 * ldv + c0;
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) zs[tn] = col0 + 16 * tn < s1 ? zsq[col0 + 16 * tn] : 0.f;
+#pragma unroll
+    for (int tm = 0; tm < 8; ++tm)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float xs = xs_s[wr * 128 + tm * 16 + 4 * (lane >> 4) + q];
+#pragma unroll
+        for (int tn = 0; tn < 4; ++tn) {    // (the form of gauss_mmv_h2w256_kernel: its bits are the contract)
+          float d2 = fmaf(m2, acc[tm][tn][q], xs) + zs[tn];
+          d2 = fmaxf(d2, 0.f);
+          acc[tm][tn][q] = __builtin_amdgcn_exp2f(d2 * gamma_log2e);
+        }
+      }
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      mmvn_fresh(acc);
+      double al[4];
+#pragma unroll
+      for (int tn = 0; tn < 4; ++tn) al[tn] = (col0 + 16 * tn < s1 && c < nc) ? vp[16 * tn * ldv + c] : 0.0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        double w8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {       // slots j (tm' = j >> 2) and j + 8 (tm' = 2 + (j >> 2)), q = j & 3
+          double v[2];
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            const int tm = 4 * h + 2 * u + (j >> 2), q = j & 3;
+            v[u] = 0.0;
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn) v[u] = fma((double)acc[tm][tn][q], al[tn], v[u]);
+          }
+          w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+        }
+        double w4[4], w2[2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
+        double* sum = c < PARK ? parked + c * 4 * W_BM + 64 * h : mine + (c - PARK) * 4 * W_BM + 64 * h;
+        *sum += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+      }
+    }
+    if (j0 + W_BN < s1) {
+#pragma unroll
+      for (int c = 0; c < NV - PARK; ++c) tot[c][0] = mine[c * 4 * W_BM], tot[c][1] = mine[c * 4 * W_BM + 64];
+    }
+    __syncthreads();                  // the next main loop writes the images at once; behind the last tile: `red` is complete
+  }
+  if (threadIdx.x < W_BM) {
+    const int64_t row = i0 + threadIdx.x;
+    if (row < n)
+      for (int c = 0; c < nc; ++c) {
+        const double* rc = (c < PARK ? &park[0][0][0] + c * 4 * W_BM : red + (c - PARK) * 4 * W_BM) + threadIdx.x;
+        slab[((int64_t)(c0 + c) * G + g) * slab_ld + row] = (rc[0] + rc[W_BM]) + (rc[2 * W_BM] + rc[3 * W_BM]);
+      }
+  }
+}
+
 constexpr int MMV_TG = 4;   // column tiles per workgroup (2 / 4 / 8 / 16 / 40 measured: 342 / 341 / 335 / 321 / 305 TF)
 
 constexpr int W_MMV_TG = 2; // column tiles per workgroup on the 256 x 256 core (1 / 2 / 4 / 8 measured: 409 / 419 / 412 / 395 TF)
@@ -2646,6 +2890,91 @@ extern "C" int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax
   hipLaunchKernelGGL(mmv_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)C), dim3(256), 0, as_stream(stream), slab,
                      slab_ld, G, tg, GEMM_BN, ranges, n, out, ldo);
   ODX_CHECK_LAUNCH("odx_gauss_mmv_h2(reduce)");
+  return ODX_OK;
+}
+
+// ---- shared-centre scoring: all T columns of a dense V from one evaluation of K per group of up to 8 columns
+struct MmvnArgs {
+  const uint32_t *PX, *PZ;
+  int64_t ldpx, ldpz, n, M, ldv, slab_ld;
+  const float *metax, *xsq, *metaz, *zsq;
+  const double* V;
+  double* slab;
+  float gamma_log2e;
+  int kt, T, tg, G;          // kt: k-tiles (128 x 128 core) or stages (256 x 256 core)
+  unsigned wgs;
+  hipStream_t stream;
+};
+
+template <int NV, bool WIDE>
+static int launch_mmvn_group(const MmvnArgs& a, int cbase, int groups) {
+  if (WIDE) {
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2w256_kernel<NV, CORE_H2>), W_LDS_BYTES));
+    hipLaunchKernelGGL((gauss_mmvn_h2w256_kernel<NV, CORE_H2>), dim3(a.wgs, (unsigned)groups), dim3(W_THREADS), W_LDS_BYTES, a.stream,
+                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, a.gamma_log2e, a.V, a.ldv, cbase,
+                       a.T, a.tg, a.G, a.slab, a.slab_ld);
+  } else {
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2s16_kernel<NV>)));
+    hipLaunchKernelGGL((gauss_mmvn_h2s16_kernel<NV>), dim3(a.wgs, (unsigned)groups), dim3(GEMM_THREADS), S16_LDS_BYTES, a.stream,
+                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, a.gamma_log2e, a.V, a.ldv, cbase,
+                       a.T, a.tg, a.G, a.slab, a.slab_ld);
+  }
+  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2");
+  return ODX_OK;
+}
+
+// the full groups of 8 columns in one launch, what remains on the next instantiated width
+template <bool WIDE>
+static int launch_mmvn(const MmvnArgs& a) {
+  const int full = a.T / 8, rest = a.T % 8;
+  if (full) ODX_PROPAGATE((launch_mmvn_group<8, WIDE>(a, 0, full)));
+  if (rest > 4) return launch_mmvn_group<8, WIDE>(a, 8 * full, 1);
+  if (rest > 2) return launch_mmvn_group<4, WIDE>(a, 8 * full, 1);
+  if (rest > 0) return launch_mmvn_group<2, WIDE>(a, 8 * full, 1);
+  return ODX_OK;
+}
+
+extern "C" int64_t odx_gauss_mmvn_h2_workspace_bytes(int64_t n, int64_t M, int T) {
+  return odx_gauss_mmv_h2_workspace_bytes(n, M, T);
+}
+
+extern "C" int odx_gauss_mmvn_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
+                                 int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma,
+                                 const double* V, int64_t ldv, int T, float* out, int64_t ldo, void* workspace,
+                                 int64_t workspace_bytes, odx_stream_t stream) {
+  if (n <= 0 || T <= 0) return ODX_OK;
+  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && out && D > 0 && sigma > 0 && ldv >= T && M > 0,
+              "odx_gauss_mmvn_h2: bad argument");
+  const int64_t dp = round_up(D, H2_KT);
+  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
+              "odx_gauss_mmvn_h2: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)");
+  ODX_REQUIRE(ldo >= T && T < 65536, "odx_gauss_mmvn_h2: ldo < T or too many columns");
+  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24), "odx_gauss_mmvn_h2: leading dimensions must stay below 2^24 (32-bit tile offsets)");
+  if (workspace == nullptr || workspace_bytes < odx_gauss_mmvn_h2_workspace_bytes(n, M, T)) {
+    set_error("odx_gauss_mmvn_h2: workspace too small");
+    return ODX_ERR_WORKSPACE;
+  }
+  MmvnArgs a;
+  a.PX = (const uint32_t*)PX, a.PZ = (const uint32_t*)PZ, a.ldpx = ldpx, a.ldpz = ldpz, a.n = n, a.M = M, a.ldv = ldv;
+  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T;
+  a.slab = static_cast<double*>(workspace), a.slab_ld = round_up(n, 2);
+  a.gamma_log2e = (float)(-0.5 / (sigma * sigma)) * LOG2E, a.stream = as_stream(stream);
+  // the tile core, the groups of column tiles and the slab of odx_gauss_mmv_h2 for T columns: the same bits per column
+  const bool wide = h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
+  int64_t wgs;
+  if (wide) {
+    a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = (int)(dp / W_KS);
+    wgs = round_up(ceil_div(n, W_BM), 8) * a.G;
+  } else {
+    a.tg = mmv_tg(n, M, T), a.G = (int)mmv_groups(M, a.tg), a.kt = (int)(dp / H2_KT);
+    wgs = round_up(ceil_div(n, GEMM_BM), 8) * a.G;
+  }
+  ODX_REQUIRE(wgs < (1ll << 31), "odx_gauss_mmvn_h2: grid too large");
+  a.wgs = (unsigned)wgs;
+  ODX_PROPAGATE(wide ? launch_mmvn<true>(a) : launch_mmvn<false>(a));
+  hipLaunchKernelGGL(mmvn_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)T), dim3(256), 0, a.stream, a.slab, a.slab_ld,
+                     a.G, n, out, ldo);
+  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2(reduce)");
   return ODX_OK;
 }
 

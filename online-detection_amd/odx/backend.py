@@ -106,6 +106,11 @@ class KnmStream:
 
 class HipBackend(PathOps):
     name = "hip-gfx950"
+    # The smallest number of columns for which a dense mmv (ranges None, gauss "h2") goes through odx_gauss_mmvn_h2: K(X, Z)
+    # evaluated once per group of up to 8 columns instead of once per column, the same bits.  An attribute like
+    # wide_pass_min, not an option; None = never.  2: the route won at every measured shape from two columns on
+    # (profiles/mmv_shared.md).
+    shared_mmv_min = 2
 
     def __init__(self, device=None):
         self.lib = hip.require_gpu()
@@ -660,10 +665,24 @@ class HipBackend(PathOps):
         V = V.to(device=self.device, dtype=torch.float64)
         if V.dim() == 1:
             V = V[:, None]
+        Vs = V                   # (the shared-centre entry takes any leading dimension: no copy of a column block)
         V = V.contiguous()
         Mtot, T = V.shape
         if Mtot != Zf.n:
             raise ValueError("mmv: V has %d rows but there are %d centres" % (Mtot, Zf.n))
+        shared = ranges is None and self.gauss == "h2" and self.shared_mmv_min is not None and T >= self.shared_mmv_min
+        if shared and F.n > 0 and T > 0 and Mtot > 0:
+            # all columns weigh all centres: one evaluation of K per group of up to 8 columns (the per-column launch's bits)
+            if out is None:
+                out = torch.empty((F.n, T), dtype=torch.float32, device=self.device)
+            self.pack(F), self.pack(Zf)
+            if Vs.stride(1) == 1 and Vs.stride(0) >= T:
+                V = Vs
+            ws = self._workspace("mmv", self.lib.odx_gauss_mmvn_h2_workspace_bytes(F.n, Mtot, T))
+            hip.check(self.lib.odx_gauss_mmvn_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), F.n, _p(Zf.P), Zf.P.stride(0),
+                                                 _p(Zf.meta), _p(Zf.sq), Mtot, F.D, float(sigma), _p(V), V.stride(0), T,
+                                                 _p(out), out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_mmvn_h2")
+            return out
         if ranges is None:
             key = ("dense_ranges", Mtot, T)          # a host -> device copy per call otherwise (a predict is ~50 us of GPU work)
             ranges = self._ws.get(key)

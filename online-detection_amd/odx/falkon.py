@@ -50,16 +50,19 @@ class GaussianKernel:
     def __init__(self, sigma, opt=None):
         self.sigma = float(sigma)
 
-    def mmv(self, X1, X2, v, out=None, opt=None):
+    def mmv(self, X1, X2, v, out=None, opt=None, dense=False):
         """K(X1, X2) @ v -> (n, T) f32.  A block-structured v (the heads' alpha_parallel) is
-        detected and only its non-zero row range per column is visited."""
+        detected and only its non-zero row range per column is visited.  ``dense=True``: every column weighs every
+        centre (a multi-output model, the members of a lambda path) — no ranges are looked for and the backend may
+        evaluate K once for all columns (HipBackend.shared_mmv_min).  For a fitted model this is today's result bit
+        for bit: the range of a column whose first and last entries are non-zero is [0, M) anyway."""
         be = _backend.get_backend()
         F = be.features(X1)
         Zf = X2 if (hasattr(X2, "sq") or hasattr(X2, "n")) and not torch.is_tensor(X2) else be.features(X2)     # a backend's Features
         v = torch.as_tensor(v)
         if v.dim() == 1:
             v = v[:, None]
-        ranges = block_ranges(v) if v.shape[1] > 1 else None      # one column (model.predict): every centre counts
+        ranges = block_ranges(v) if v.shape[1] > 1 and not dense else None      # one column (model.predict): every centre counts
         res = be.mmv(F, Zf, self.sigma, v, ranges)
         if out is not None:
             out.copy_(res)
@@ -211,13 +214,47 @@ class _FalkonBase:
     def predict(self, X):
         if self.alpha_ is None:
             raise RuntimeError("predict called before fit")
-        res = self.kernel.mmv(X, self._centres(), self.alpha_)
+        if self.alpha_.dim() == 2 and self.alpha_.shape[1] > 1:     # a multi-output model: all columns share the centres
+            res = self.kernel.mmv(X, self._centres(), self.alpha_, dense=True)
+        else:
+            res = self.kernel.mmv(X, self._centres(), self.alpha_)
         if self._cpu_model and not (torch.is_tensor(X) and X.is_cuda):
             res = res.cpu()
         return res
 
     def __bool__(self):
         return True
+
+
+def _same_tensor(a, b):
+    return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape
+                      and a.stride() == b.stride() and a.dtype == b.dtype and a.device == b.device)
+
+
+def predict_path(estimators, X):
+    """(n, L) f32: column l is ``estimators[l].predict(X)[:, 0]``, bit for bit, from ONE dense mmv over the stacked
+    alphas — the members of a ``fit_path``, or any fitted estimators that share their centres (one ``ny_points_``
+    tensor), sigma and have one output each.  Scoring a path on held-out rows then costs one contraction where the
+    backend evaluates K once for all columns (HipBackend.shared_mmv_min) instead of L.  The first member's centre
+    cache is used; a host model (``Falkon``) returns a host tensor for host rows, as ``predict`` does."""
+    estimators = list(estimators)
+    if not estimators:
+        raise ValueError("predict_path: no estimators")
+    first = estimators[0]
+    for est in estimators:
+        if est.alpha_ is None or est.ny_points_ is None:
+            raise RuntimeError("predict_path called before fit")
+        if not _same_tensor(est.ny_points_, first.ny_points_):
+            raise ValueError("predict_path: the estimators must share one ny_points_ tensor (the members of a fit_path do)")
+        if float(est.kernel.sigma) != float(first.kernel.sigma):
+            raise ValueError("predict_path: the estimators must share sigma, got %g and %g" % (first.kernel.sigma, est.kernel.sigma))
+        if est.alpha_.dim() != 2 or tuple(est.alpha_.shape) != (first.ny_points_.shape[0], 1):
+            raise ValueError("predict_path: every alpha_ must be (M, 1), got %s" % (tuple(est.alpha_.shape),))
+    V = torch.cat([est.alpha_ for est in estimators], dim=1)
+    res = first.kernel.mmv(X, first._centres(), V, dense=True)
+    if first._cpu_model and not (torch.is_tensor(X) and X.is_cuda):
+        res = res.cpu()
+    return res
 
 
 def fit_batch(estimators, Xs, Ys, streams=None):

@@ -61,6 +61,9 @@ SIGNATURES = {
     "odx_gauss_mmv_h2_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "odx_gauss_mmv_h2": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _vp, _i64, _vp, _i32, _vp, _i64,
                                 _vp, _i64, _vp]),
+    "odx_gauss_mmvn_h2_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "odx_gauss_mmvn_h2": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _vp, _i64, _i32, _vp, _i64,
+                                 _vp, _i64, _vp]),
     "odx_falkon_cg_workspace_bytes": (_i64, [_i64, _i64]),
     "odx_falkon_cg_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _f64, _i32, _i32, _f64, _f64, _vp, _vp,
                                  _i64, _vp]),
