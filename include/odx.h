@@ -249,6 +249,31 @@ int odx_knm_fwd_bwd_q_t(const void* K, int64_t ldk, const void* Klo, int64_t ldl
 int odx_knm_fwd_bwd2_q_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
                          const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
                          int64_t workspace_bytes, odx_stream_t stream);
+/* Distinct columns.  A centre list drawn with replacement names some centres more than once, and the columns of K_nM at
+ * the repeats are copies.  A block may then hold the M DISTINCT columns only (in order of first occurrence: a column
+ * subsequence of the full block) while every vector keeps the list's length Mv >= M.  The column map says which is which:
+ *   col_of (Mv int32)     col_of[j] = the column of list position j
+ *   start  (M + 1 int32), pos (Mv int32)   the positions of column d are pos[start[d] .. start[d + 1]), ascending
+ * With K the stored block and K_full the Mv-column one:  K_full v = K fold(v),  fold(v)[d] = the sum of v[pos[k]] over
+ * column d's positions (left to right, from 0.0), and  (K_full' t)[j] = (K' t)[col_of[j]].
+ * odx_knm_fwd_bwd_q_cols_t / odx_knm_fwd_bwd2_q_cols_t are odx_knm_fwd_bwd_q_t / odx_knm_fwd_bwd2_q_t over such a block:
+ * v, v2, out, out2 are Mv long; K, ldk, M, t_out, w and the workspace (odx_knm_fwd_bwd[2]_q_workspace_bytes(n, M, fmt))
+ * are those of the M-column block.  The same kernels run: the fold happens where they load v into LDS, the final reduce
+ * writes out[j] from column col_of[j]; the streaming loop is unchanged.  out (out2) equals, bit for bit,
+ * odx_cols_expand_f64 of what the plain entry returns for v = odx_cols_fold_f64(v), and t_out is that call's t_out.
+ * Indices read from the map are clamped into their ranges (a malformed map gives wrong sums, no access out of range).
+ * odx_cols_fold_f64:   out[d] = fold(v)[d], d < M.      odx_cols_expand_f64: out[j] = x[col_of[j]], j < Mv. */
+int odx_knm_fwd_bwd_q_cols_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                             const double* v, const double* w, double* out, double* t_out, void* workspace,
+                             int64_t workspace_bytes, int64_t Mv, const int32_t* col_of, const int32_t* start,
+                             const int32_t* pos, odx_stream_t stream);
+int odx_knm_fwd_bwd2_q_cols_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                              const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
+                              int64_t workspace_bytes, int64_t Mv, const int32_t* col_of, const int32_t* start,
+                              const int32_t* pos, odx_stream_t stream);
+int odx_cols_fold_f64(const double* v, int64_t Mv, const int32_t* start, const int32_t* pos, int64_t M, double* out,
+                      odx_stream_t stream);
+int odx_cols_expand_f64(const double* x, int64_t M, const int32_t* col_of, int64_t Mv, double* out, odx_stream_t stream);
 /* out[q] = K' (K v[q]), q = 0 .. nv - 1, 3 <= nv <= 8, from ONE read of a compact-format block (what a lambda path's CG
  * states share: odx.solver.falkon_fit_path).  V / out: nv f64 rows, ldv / ldo doubles apart (even, >= M), 16-byte aligned.
  * The vectors sit whole in LDS as f64, so the widths that exist are nv <= 8 up to M = 2524 and nv <= 4 up to M = 5084; the

@@ -2,6 +2,7 @@
 // state[0] = rs_old, state[1] = rs_new, state[2] = stop flag (0 / 1), state[3] = last step size.
 // One 1024-thread workgroup per call: M <= ~20k, so these are latency-sized, not bandwidth-sized.
 #include "odx_internal.h"
+#include "knm_q.h"
 
 namespace odx {
 
@@ -156,6 +157,24 @@ __global__ __launch_bounds__(256) void cg_scores_store_kernel(const double* __re
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) out[i * ldo] = (float)S[i];
 }
 
+// out[d] = fold(v)[d], d < M: the sum of v over the positions of distinct column d (knm_q.h, cols_fold_entry)
+__global__ __launch_bounds__(256) void cols_fold_kernel(const double* __restrict__ v, int64_t Mv, const int* __restrict__ start,
+                                                        const int* __restrict__ pos, int64_t M, double* __restrict__ out) {
+  const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (d < M) out[d] = cols_fold_entry(v, d, Mv, start, pos);
+}
+
+// out[j] = x[col_of[j]], j < Mv (col_of clamped to [0, M))
+__global__ __launch_bounds__(256) void cols_expand_kernel(const double* __restrict__ x, int64_t M, const int* __restrict__ col_of,
+                                                          int64_t Mv, double* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < Mv) {
+    int64_t d = col_of[j];
+    d = d < 0 ? 0 : (d >= M ? M - 1 : d);
+    out[j] = x[d];
+  }
+}
+
 __global__ __launch_bounds__(256) void axpby_kernel(double a, const double* __restrict__ x, double b,
                                                     double* __restrict__ y, int64_t M) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -264,5 +283,22 @@ extern "C" int odx_axpby_f64(double a, const double* x, double b, double* y, int
   ODX_REQUIRE(x && y, "odx_axpby_f64: null pointer");
   hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, as_stream(stream), a, x, b, y, M);
   ODX_CHECK_LAUNCH("odx_axpby_f64");
+  return ODX_OK;
+}
+
+extern "C" int odx_cols_fold_f64(const double* v, int64_t Mv, const int32_t* start, const int32_t* pos, int64_t M, double* out,
+                                 odx_stream_t stream) {
+  if (M <= 0) return ODX_OK;
+  ODX_REQUIRE(v && start && pos && out && Mv >= M && Mv <= INT32_MAX, "odx_cols_fold_f64: null pointer or Mv < M");
+  hipLaunchKernelGGL(cols_fold_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, as_stream(stream), v, Mv, start, pos, M, out);
+  ODX_CHECK_LAUNCH("odx_cols_fold_f64");
+  return ODX_OK;
+}
+
+extern "C" int odx_cols_expand_f64(const double* x, int64_t M, const int32_t* col_of, int64_t Mv, double* out, odx_stream_t stream) {
+  if (Mv <= 0) return ODX_OK;
+  ODX_REQUIRE(x && col_of && out && M > 0 && Mv >= M, "odx_cols_expand_f64: null pointer or Mv < M");
+  hipLaunchKernelGGL(cols_expand_kernel, dim3((unsigned)ceil_div(Mv, 256)), dim3(256), 0, as_stream(stream), x, M, col_of, Mv, out);
+  ODX_CHECK_LAUNCH("odx_cols_expand_f64");
   return ODX_OK;
 }

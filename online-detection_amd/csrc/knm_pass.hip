@@ -419,6 +419,26 @@ __global__ __launch_bounds__(256) void slab_reduce2_kernel(const double* __restr
   if (wave == 0 && j < M) (blockIdx.y ? out2 : out)[j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
 
+// slab_reduce_kernel / slab_reduce2_kernel read through a column map: output j < Mv takes the sum of column col_of[j] of the
+// M the slabs hold, in the same order (blockIdx.y: the vector of a slab of nv)
+__global__ __launch_bounds__(256) void slab_reduce_cols_kernel(const double* __restrict__ slab, int64_t slab_ld, int nslab, int nv,
+                                                               int64_t M, int64_t Mv, const int* __restrict__ col_of,
+                                                               double* __restrict__ out, double* __restrict__ out2) {
+  __shared__ double part[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t j = (int64_t)blockIdx.x * 64 + lane;
+  const double* base = slab + (int64_t)blockIdx.y * slab_ld;
+  double s = 0.0;
+  if (j < Mv) {
+    int64_t d = col_of[j];
+    d = d < 0 ? 0 : (d >= M ? M - 1 : d);
+    s = slab_column_sum(base + d, nv * slab_ld, nslab, wave);
+  }
+  part[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && j < Mv) (blockIdx.y ? out2 : out)[j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+}
+
 static int g_reserved_cus = 0;
 
 struct PassCfg {
@@ -559,6 +579,14 @@ int odx::slab_reduce_batched_f64(int B, const int64_t* M, const int* nslab, cons
 int odx::slab_reduce_f64(const double* slab, int64_t slab_ld, int nslab, int64_t M, double* out, hipStream_t s) {
   hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(M, 64)), dim3(256), 0, s, slab, slab_ld, nslab, M, out);
   ODX_CHECK_LAUNCH("slab_reduce_f64");
+  return ODX_OK;
+}
+
+int odx::slab_reduce_cols_f64(const double* slab, int64_t slab_ld, int nslab, int nv, int64_t M, int64_t Mv, const int* col_of,
+                              double* out, double* out2, hipStream_t s) {
+  hipLaunchKernelGGL(slab_reduce_cols_kernel, dim3((unsigned)ceil_div(Mv, 64), (unsigned)nv), dim3(256), 0, s, slab, slab_ld, nslab, nv,
+                     M, Mv, col_of, out, out2);
+  ODX_CHECK_LAUNCH("slab_reduce_cols_f64");
   return ODX_OK;
 }
 

@@ -30,7 +30,8 @@ __device__ __forceinline__ void knm_passq_body(const unsigned short* __restrict_
                                                const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                int64_t M, const double* __restrict__ v1, const double* __restrict__ v2,
                                                const double* __restrict__ w, double* __restrict__ slab, int64_t slab_ld,
-                                               double* __restrict__ t_out, int wg, int nwg) {
+                                               double* __restrict__ t_out, int wg, int nwg, int64_t Mv = 0,
+                                               const int* __restrict__ cstart = nullptr, const int* __restrict__ cpos = nullptr) {
   constexpr int NW = NT / 64;
   constexpr int CW = QCW;
   extern __shared__ __attribute__((aligned(16))) double vsq[];       // [NV][vcap]
@@ -40,9 +41,11 @@ __device__ __forceinline__ void knm_passq_body(const unsigned short* __restrict_
   const int vcap = (nchunk + 1) * CW;      // one chunk of zeros behind the row: where the chunks past the row's end point
   const int64_t nblk = (n + R - 1) / R;
   const double vscale = FMT == QF_U24 ? 5.9604644775390625e-08 : 1.0;      // 2^-24 (exact)
+  // (cstart set: the block holds the DISTINCT columns of an Mv-long centre list, slot i receives the sum of v over the
+  // positions of column i — q_v_entry; null: v[i] itself)
   for (int i = tid; i < vcap; i += NT) {
-    vsq[i] = (v1 != nullptr && i < M) ? v1[i] * vscale : 0.0;
-    if (NV == 2) vsq[vcap + i] = i < M ? v2[i] * vscale : 0.0;
+    vsq[i] = (v1 != nullptr && i < M) ? q_v_entry(v1, i, Mv, cstart, cpos) * vscale : 0.0;
+    if (NV == 2) vsq[vcap + i] = i < M ? q_v_entry(v2, i, Mv, cstart, cpos) * vscale : 0.0;
   }
   double acc[NV][CH][CW];
 #pragma unroll
@@ -216,8 +219,10 @@ __global__ __launch_bounds__(NT, WPE) void knm_passq_kernel(const unsigned short
                                                        const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                        int64_t M, const double* __restrict__ v1, const double* __restrict__ v2,
                                                        const double* __restrict__ w, double* __restrict__ slab, int64_t slab_ld,
-                                                       double* __restrict__ t_out) {
-  knm_passq_body<NT, CH, R, NV, FMT, WPE>(Khi, ldk, Klo, ldlo, n, M, v1, v2, w, slab, slab_ld, t_out, (int)blockIdx.x, (int)gridDim.x);
+                                                       double* __restrict__ t_out, int64_t Mv, const int* __restrict__ cstart,
+                                                       const int* __restrict__ cpos) {
+  knm_passq_body<NT, CH, R, NV, FMT, WPE>(Khi, ldk, Klo, ldlo, n, M, v1, v2, w, slab, slab_ld, t_out, (int)blockIdx.x, (int)gridDim.x, Mv,
+                                          cstart, cpos);
 }
 
 // The classes of a batch by one launch (blockIdx.y = class): class b's block is walked by grid[b] workgroups exactly as its
@@ -260,7 +265,9 @@ __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __rest
                                                     const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                     int64_t M, const double* __restrict__ v1,
                                                     const double* __restrict__ w, double* __restrict__ slab,
-                                                    int64_t slab_ld, double* __restrict__ t_out, int wg, int nwg) {
+                                                    int64_t slab_ld, double* __restrict__ t_out, int wg, int nwg,
+                                                    int64_t Mv = 0, const int* __restrict__ cstart = nullptr,
+                                                    const int* __restrict__ cpos = nullptr) {
   constexpr int NT = 256, CW = QCW;
   extern __shared__ __attribute__((aligned(16))) double vsq[];
   __shared__ double red[2][2][4][R];                 // [half][ping-pong][wave of the half][row]
@@ -275,7 +282,7 @@ __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __rest
   constexpr int vcap = CH * NT * CW;
   const int64_t nblk = (n + R - 1) / R;
   const double vscale = FMT == QF_U24 ? 5.9604644775390625e-08 : 1.0;
-  for (int i = tid; i < vcap; i += 512) vsq[i] = (v1 != nullptr && i < M) ? v1[i] * vscale : 0.0;
+  for (int i = tid; i < vcap; i += 512) vsq[i] = (v1 != nullptr && i < M) ? q_v_entry(v1, i, Mv, cstart, cpos) * vscale : 0.0;
   const int voff_hi = ht * (2 * CW), voff_lo = ht * CW;
   double acc[CH][CW];
 #pragma unroll
@@ -428,8 +435,9 @@ __global__ __launch_bounds__(512, 2) void knm_passq_stag_kernel(const unsigned s
                                                                 const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                                 int64_t M, const double* __restrict__ v1,
                                                                 const double* __restrict__ w, double* __restrict__ slab,
-                                                                int64_t slab_ld, double* __restrict__ t_out) {
-  knm_passq_stag_body<CH, R, FMT>(Khi, ldk, Klo, ldlo, n, M, v1, w, slab, slab_ld, t_out, (int)blockIdx.x, (int)gridDim.x);
+                                                                int64_t slab_ld, double* __restrict__ t_out, int64_t Mv,
+                                                                const int* __restrict__ cstart, const int* __restrict__ cpos) {
+  knm_passq_stag_body<CH, R, FMT>(Khi, ldk, Klo, ldlo, n, M, v1, w, slab, slab_ld, t_out, (int)blockIdx.x, (int)gridDim.x, Mv, cstart, cpos);
 }
 
 template <int CH, int R, int FMT>
@@ -498,13 +506,13 @@ static int qgrid_for(const QCfg& cfg, int64_t n) {
 // of NV = 2; w: NV = 1 only.)
 template <int NV, int FMT>
 static int dispatch_passq(const QCfg& cfg, const QBlock& b, int grid, size_t lds, hipStream_t s, const double* v, const double* v2,
-                          const double* w, double* slab, int64_t slab_ld, double* t_out) {
+                          const double* w, double* slab, int64_t slab_ld, double* t_out, const QCols& cm) {
 #define ODX_Q(NT_, CH_, R_)                                                                                                      \
   return q_launch(knm_passq_kernel<NT_, CH_, R_, NV, FMT, (NT_ >= 1024 ? 4 : 2)>, dim3(grid), NT_, lds, s, b.hi, b.ldk, b.lo, b.ldlo, \
-                  b.n, b.M, v, v2, w, slab, slab_ld, t_out)
+                  b.n, b.M, v, v2, w, slab, slab_ld, t_out, cm.Mv, cm.start, cm.pos)
 #define ODX_QH(CH_, R_)                                                                                                          \
   return q_launch(knm_passq_stag_kernel<CH_, R_, FMT>, dim3(grid), 512, lds, s, b.hi, b.ldk, b.lo, b.ldlo, b.n, b.M, v, w, slab,  \
-                  slab_ld, t_out)
+                  slab_ld, t_out, cm.Mv, cm.start, cm.pos)
   if constexpr (NV == 1) {
     if (cfg.nt == 0) {
       if (cfg.ch == 2) ODX_QH(2, 8);
@@ -660,14 +668,21 @@ extern "C" int64_t odx_knm_fwd_bwd_q_workspace_bytes(int64_t n, int64_t M, int f
   return (int64_t)workspace_cus() * (cfg.nt == 0 ? 2 * cfg.wg_per_cu : cfg.wg_per_cu) * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
-// (t_out: the _t entry's extra output, null for the plain one — same kernels, same slabs, same out either way)
+// The column map of a _cols entry has all three index vectors and Mv >= M (what can be checked without reading them).
+static int check_q_cols(const char* who, const QCols& cm, int64_t M) {
+  ODX_REQUIRE(cm.Mv >= M && cm.Mv <= INT32_MAX && cm.col_of && cm.start && cm.pos, "%s: needs Mv >= M and col_of, start, pos", who);
+  return ODX_OK;
+}
+
+// (t_out: the _t entry's extra output, null for the plain one — same kernels, same slabs, same out either way.  cm: the
+// column map of the _cols entries, empty for every other: v and out are then cm.Mv long, the block and the slabs M wide)
 static int knm_fwd_bwd_q_impl(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
                               const double* v, const double* w, double* out, double* t_out, void* workspace,
-                              int64_t workspace_bytes, odx_stream_t stream) {
+                              int64_t workspace_bytes, odx_stream_t stream, const QCols& cm = QCols()) {
   ODX_REQUIRE(M > 0 && out, "odx_knm_fwd_bwd_q: M <= 0 or null out");
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
-    ODX_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)M * sizeof(double), s));
+    ODX_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)(cm.on() ? cm.Mv : M) * sizeof(double), s));
     return ODX_OK;
   }
   ODX_REQUIRE(v || w, "odx_knm_fwd_bwd_q: both v and w null");
@@ -686,9 +701,10 @@ static int knm_fwd_bwd_q_impl(const void* K, int64_t ldk, const void* Klo, int64
   // (the halves kernel keeps v zero-filled up to the 10 x 256 chunks of four its threads walk)
   const size_t lds = (cfg.nt == 0 ? (size_t)(cfg.ch * 256 * 4) : (size_t)(slab_ld + 4)) * sizeof(double);      // + the zero chunk
   ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
-    return dispatch_passq<1, decltype(f)::value>(cfg, b, grid, lds, s, v, nullptr, w, slab, slab_ld, t_out);
+    return dispatch_passq<1, decltype(f)::value>(cfg, b, grid, lds, s, v, nullptr, w, slab, slab_ld, t_out, cm);
   }));
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwd_q");
+  if (cm.on()) return slab_reduce_cols_f64(slab, slab_ld, nslab, 1, M, cm.Mv, cm.col_of, out, nullptr, s);
   return slab_reduce_f64(slab, slab_ld, nslab, M, out, s);
 }
 
@@ -714,12 +730,12 @@ extern "C" int64_t odx_knm_fwd_bwd2_q_workspace_bytes(int64_t n, int64_t M, int 
 
 static int knm_fwd_bwd2_q_impl(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
                                const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
-                               int64_t workspace_bytes, odx_stream_t stream) {
+                               int64_t workspace_bytes, odx_stream_t stream, const QCols& cm = QCols()) {
   ODX_REQUIRE(M > 0 && out && out2, "odx_knm_fwd_bwd2_q: M <= 0 or null out");
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
-    ODX_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)M * sizeof(double), s));
-    ODX_CHECK_HIP(hipMemsetAsync(out2, 0, (size_t)M * sizeof(double), s));
+    ODX_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)(cm.on() ? cm.Mv : M) * sizeof(double), s));
+    ODX_CHECK_HIP(hipMemsetAsync(out2, 0, (size_t)(cm.on() ? cm.Mv : M) * sizeof(double), s));
     return ODX_OK;
   }
   ODX_REQUIRE(v && v2, "odx_knm_fwd_bwd2_q: null v or v2");
@@ -735,9 +751,10 @@ static int knm_fwd_bwd2_q_impl(const void* K, int64_t ldk, const void* Klo, int6
   double* slab = static_cast<double*>(workspace);
   const size_t lds = (size_t)(2 * (slab_ld + 4) * sizeof(double));      // two vectors, each with its zero chunk
   ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
-    return dispatch_passq<2, decltype(f)::value>(cfg, b, grid, lds, s, v, v2, nullptr, slab, slab_ld, t_out);
+    return dispatch_passq<2, decltype(f)::value>(cfg, b, grid, lds, s, v, v2, nullptr, slab, slab_ld, t_out, cm);
   }));
   ODX_CHECK_LAUNCH("odx_knm_fwd_bwd2_q");
+  if (cm.on()) return slab_reduce_cols_f64(slab, slab_ld, grid, 2, M, cm.Mv, cm.col_of, out, out2, s);
   return slab_reduce2_f64(slab, slab_ld, grid, M, out, out2, s);
 }
 
@@ -751,4 +768,25 @@ extern "C" int odx_knm_fwd_bwd2_q_t(const void* K, int64_t ldk, const void* Klo,
                                     const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
                                     int64_t workspace_bytes, odx_stream_t stream) {
   return knm_fwd_bwd2_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, v2, out, out2, t_out, workspace, workspace_bytes, stream);
+}
+
+// The same two passes over a block that holds the DISTINCT columns of an Mv-long centre list (see include/odx.h): v / out are
+// Mv long, the block, its slabs and the workspace are those of its M columns.
+extern "C" int odx_knm_fwd_bwd_q_cols_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                        const double* v, const double* w, double* out, double* t_out, void* workspace,
+                                        int64_t workspace_bytes, int64_t Mv, const int32_t* col_of, const int32_t* start,
+                                        const int32_t* pos, odx_stream_t stream) {
+  ODX_REQUIRE(t_out == nullptr || v != nullptr, "odx_knm_fwd_bwd_q_cols_t: t_out needs v");
+  const QCols cm = {Mv, col_of, start, pos};
+  ODX_PROPAGATE(check_q_cols("odx_knm_fwd_bwd_q_cols_t", cm, M));
+  return knm_fwd_bwd_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, w, out, t_out, workspace, workspace_bytes, stream, cm);
+}
+
+extern "C" int odx_knm_fwd_bwd2_q_cols_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                         const double* v, const double* v2, double* out, double* out2, double* t_out,
+                                         void* workspace, int64_t workspace_bytes, int64_t Mv, const int32_t* col_of,
+                                         const int32_t* start, const int32_t* pos, odx_stream_t stream) {
+  const QCols cm = {Mv, col_of, start, pos};
+  ODX_PROPAGATE(check_q_cols("odx_knm_fwd_bwd2_q_cols_t", cm, M));
+  return knm_fwd_bwd2_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, v2, out, out2, t_out, workspace, workspace_bytes, stream, cm);
 }

@@ -36,6 +36,43 @@ __device__ __forceinline__ double q_entry(const QChunk<FMT, CW>& k, int e) {
   return (double)__uint_as_float((e & 1) ? (h & 0xffff0000u) : (h << 16));
 }
 
+// ---------------------------------------------------------------------------------------------------- distinct columns
+// A block may hold only the DISTINCT columns of a centre list of Mv positions that names some centres more than once
+// (M <= Mv columns, in order of first occurrence).  The map: col_of[j] = the column of position j; start / pos = the
+// positions of every column as a CSR list, ascending (start has M + 1 entries, pos Mv).  K_full v = K fold(v) and
+// (K_full' t)[j] = (K' t)[col_of[j]].  Every index read from the map is clamped into its range: a malformed map gives wrong
+// sums, never an access outside v or the slabs.
+struct QCols {
+  int64_t Mv = 0;
+  const int* col_of = nullptr;
+  const int* start = nullptr;
+  const int* pos = nullptr;
+  bool on() const { return start != nullptr; }
+};
+
+// fold(v)[d]: the sum of v over the positions of column d, left to right from 0.0 (the one statement of it: the pass
+// kernels' load of v and odx_cols_fold_f64 give the same bits)
+__device__ __forceinline__ double cols_fold_entry(const double* __restrict__ v, int64_t d, int64_t Mv, const int* __restrict__ start,
+                                                  const int* __restrict__ pos) {
+  const int last = (int)Mv - 1;
+  int k = start[d], e = start[d + 1];
+  k = k < 0 ? 0 : k;
+  e = e > (int)Mv ? (int)Mv : e;
+  double s = 0.0;
+  for (; k < e; ++k) {
+    int j = pos[k];
+    j = j < 0 ? 0 : (j > last ? last : j);
+    s += v[j];
+  }
+  return s;
+}
+
+// what slot i of a pass kernel's copy of v receives: v[i], or with a column map fold(v)[i]
+__device__ __forceinline__ double q_v_entry(const double* __restrict__ v, int64_t i, int64_t Mv, const int* __restrict__ start,
+                                            const int* __restrict__ pos) {
+  return start == nullptr ? v[i] : cols_fold_entry(v, i, Mv, start, pos);
+}
+
 // ---------------------------------------------------------------------------------------------------- host side
 // A compact block as the entries receive it.  The launches unpack it into the kernels' parameters.
 struct QBlock {

@@ -77,6 +77,11 @@ int slab_reduce_f64(const double* slab, int64_t slab_ld, int nslab, int64_t M, d
 // the same for the two vectors a two-product pass leaves per workgroup (slab g = [sums of v | sums of v2], 2 slab_ld apart)
 int slab_reduce2_f64(const double* slab, int64_t slab_ld, int nslab, int64_t M, double* out, double* out2, hipStream_t stream);
 
+// the same sums read through a column map (knm_q.h, QCols): out[j] = the sum of column col_of[j] (clamped to [0, M)) of the M
+// the slabs hold, j < Mv, for the nv = 1 or 2 vectors of a slab (out2: the second's) — bit for bit the sums of the two above
+int slab_reduce_cols_f64(const double* slab, int64_t slab_ld, int nslab, int nv, int64_t M, int64_t Mv, const int* col_of, double* out,
+                         double* out2, hipStream_t stream);
+
 int slab_reduce_batched_f64(int B, const int64_t* M, const int* nslab, const double* slab, int64_t slab_ld, int64_t slab_stride,
                             double* out, int64_t ostride, hipStream_t stream);
 // knm_pass_q.hip: the CG pass over compact-format blocks (24-bit fixed point / bf16) for a batch of classes

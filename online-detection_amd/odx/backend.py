@@ -26,7 +26,7 @@ from .knm_path import PathOps, _p
 class Features:
     """Row-major f32 rows (n x D, leading dimension a multiple of 4) plus their squared norms and, once a
     Gaussian-kernel call has needed it, the packed two-term f16 split of the rows (P, meta: odx_split_f16)."""
-    __slots__ = ("X", "sq", "n", "D", "ld", "P", "meta", "own_pack", "P8", "meta8", "sq8", "zero_row")
+    __slots__ = ("X", "sq", "n", "D", "ld", "P", "meta", "own_pack", "P8", "meta8", "sq8", "zero_row", "cmap")
 
     def __init__(self, X, sq, D, P=None, meta=None):
         self.X, self.sq, self.n, self.D, self.ld = X, sq, X.shape[0], D, X.stride(0) if X.shape[0] else X.shape[1]
@@ -34,6 +34,7 @@ class Features:
         self.zero_row = False           # P is followed by one all-zero row in memory (what the tap-gathering products read outside the map)
         self.own_pack = P is None       # False: P was gathered from another matrix's split and carries ITS scale
         self.P8 = self.meta8 = self.sq8 = None     # e4m3 packing (odx_split_f8), made on demand by the throughput-only fp8 kernels
+        self.cmap = None                # centres that repeat: their odx.cols.ColumnMap (knm_rhs then stores the distinct columns only)
 
 
 class Rows16:
@@ -68,11 +69,13 @@ class Precond:
 class Knm:
     """A stored K_nM shard.  fmt "f32": K (n, ld) f32.  "u24": 24-bit fixed point — K (n, ld) int16 holds q >> 8 and lo
     (n, ld) uint8 holds q & 255, q = round(K 2^24).  "bf16": K (n, ld) int16 holds the bf16 bit patterns.  (include/odx.h,
-    "compact storage of the stored K_nM")."""
-    __slots__ = ("K", "n", "M", "ld", "fmt", "lo")
+    "compact storage of the stored K_nM").  cmap (odx.cols.ColumnMap) set: a compact block of the M DISTINCT columns of a
+    centre list of Mv positions; the passes and knm_mv over it take and return Mv-long vectors (include/odx.h, "Distinct
+    columns").  Without one (None) M is the vectors' length too."""
+    __slots__ = ("K", "n", "M", "ld", "fmt", "lo", "cmap", "Mv")
 
     def __init__(self):
-        self.fmt, self.lo = "f32", None
+        self.fmt, self.lo, self.cmap, self.Mv = "f32", None, None, None
 
     def dense(self):
         """The block as an (n, M) f32 tensor (tests, diagnostics; exact for every format)."""
@@ -89,6 +92,7 @@ class Knm:
         sub.n, sub.M, sub.ld, sub.fmt = hi - lo, self.M, self.ld, self.fmt
         sub.K = self.K[lo:hi]
         sub.lo = self.lo[lo:hi] if self.lo is not None else None
+        sub.cmap, sub.Mv = self.cmap, self.Mv
         return sub
 
 
@@ -529,6 +533,17 @@ class HipBackend(PathOps):
             K = KnmStream(F, Zf, sigma, ring)
             w = None if w is None else w.to(dtype=torch.float64, device=self.device).contiguous()
             return K, self.ktk(K, w=w, out=rhs_out)
+        cmap = getattr(Zf, "cmap", None)
+        if cmap is not None and fmt in ("u24", "bf16") and n > 0:
+            # centres that repeat: the block of the DISTINCT centres (the same build kernel over the same operand rows, picked
+            # from the full list's packing: its columns are the full block's), K' w expanded to the list's M positions
+            self.pack8(Zf) if self.gauss == "f8" else self.pack(Zf)
+            first, col_of = cmap.on(self.device)[:2]
+            K, b_d = self._knm_store(F, self.rows(Zf, first), sigma, fmt, w, out, None)
+            K.cmap, K.Mv = cmap, M
+            if w is not None:
+                self._call("odx_cols_expand_f64", _p(b_d), K.M, _p(col_of), M, _p(rhs_out))
+            return K, rhs_out
         if (fmt != "f32" or self.gauss == "f8") and n > 0:
             return self._knm_store(F, Zf, sigma, fmt, w, out, rhs_out)
         if not (self.gauss == "h2" and n > 0 and self.lib.odx_gauss_h2_tile(n, M) == 256) or self.direct_small(n, M, F.D):

@@ -86,6 +86,11 @@ SIGNATURES = {
     "odx_knm_fwd_bwd2_t": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_knm_fwd_bwd_q_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_knm_fwd_bwd2_q_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "odx_knm_fwd_bwd_q_cols_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "odx_knm_fwd_bwd2_q_cols_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+                                         _vp]),
+    "odx_cols_fold_f64": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "odx_cols_expand_f64": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "odx_cg_scores_axpy_f64": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "odx_cg_scores_store_f32": (_i32, [_vp, _i64, _vp, _i64, _vp]),
     "odx_knm_fwd_bwd_q_workspace_bytes": (_i64, [_i64, _i64, _i32]),

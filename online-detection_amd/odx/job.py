@@ -19,6 +19,7 @@ import contextlib
 
 import torch
 
+from . import cols as _cols
 from . import plan as _plan
 from . import solver
 from .dist import RowShard
@@ -97,7 +98,7 @@ class LockstepClassJob:
     def __init__(self, be, X, n_total, M, labels, centre_idx, sigma, lam, maxiter=20, opt=None, shard=None,
                  precond_batch=0, precond_depth=2, precond_after_fit=False, classes=None, precond_cus=0, batch=0,
                  hbm_bytes=None, exchange="lockstep", gauss_on_complement=False, precond_lookahead=1, precond_cus_full_only=False,
-                 score_from_knm=True, scores_from_cg=True):
+                 score_from_knm=True, scores_from_cg=True, distinct_columns="auto"):
         """precond_batch: classes per rank and preconditioner chain (g; 0 = planned, 1 = one chain per class on `precond_depth`
         side streams); batch: classes per lock-step batch (b, a divisor of the world size; 0 = planned); hbm_bytes: the
         memory the plan may count on per rank (default: the device's, 288 GB without one).
@@ -109,7 +110,12 @@ class LockstepClassJob:
         that shard holds the f32-accurate entries (see _score); False: always recompute K(X, Z) alpha (backend.mmv).
         scores_from_cg: where this rank holds the CG state of a class (one rank, or exchange "allreduce") and that shard
         qualifies (solver.scores_from_cg), sum the scores from the row products of the CG's own passes and hand the sum to
-        knm_mv, which then does not read the shard again; with score_from_knm off, or on several lock-step ranks, it has no effect."""
+        knm_mv, which then does not read the shard again; with score_from_knm off, or on several lock-step ranks, it has no effect.
+        distinct_columns: the centre rule draws with replacement, so a class's K_nM block repeats some columns.  "auto": a
+        class with repeated centres whose shard is stored compact (u24 / bf16) and has at least 2^27 entries per rank (the
+        size bound of the automatic compact-storage rule) builds and streams its DISTINCT columns only (odx/cols.py; every
+        M-vector, the preconditioner, alpha and the scores keep their meaning, only f64 summation order moves); "force": the
+        same without the size bound (tests); False: never.  f32-stored and streamed shards never do."""
         # gauss_on_complement (with precond_cus = k > 0; an experiment, round-5 review item 1a): the K_nM builds and the scoring run
         # on a stream confined to the OTHER total - k compute units, so that chain and Gaussian workgroups never share a CU.
         # precond_lookahead = L: chain groups in flight ahead of the group being fitted (L + 1 factor blocks; 1 = round 2-5's
@@ -122,6 +128,9 @@ class LockstepClassJob:
         self.exchange = exchange
         self.score_from_knm = bool(score_from_knm)
         self.scores_from_cg = bool(scores_from_cg) and self.score_from_knm
+        if distinct_columns not in ("auto", False, "force"):
+            raise ValueError("LockstepClassJob: distinct_columns must be 'auto', False or 'force', got %r" % (distinct_columns,))
+        self.distinct_columns = distinct_columns
         if exchange == "allreduce":
             batch = 1                             # one stored K_nM shard in flight; the plan's b = 1 line is this mode's memory
         self.be, self.X, self.N, self.M = be, X, int(n_total), int(M)
@@ -170,6 +179,7 @@ class LockstepClassJob:
         self.gside = _Side(dev, be, 0 if self.full_only else precond_cus) if grouped else None
         self.cside = _Side(dev, be, precond_cus, index=1) if (grouped and self.full_only) else None
         self._cplans = {}        # class -> the centre-assembly plan of gather_centres (world > 1)
+        self._cmaps = {}         # class -> the column map of its repeated centres (distinct_columns), where it has one
         self.gauss_stream = (be.masked_stream(precond_cus, complement=True)
                              if gauss_on_complement and precond_cus > 0 and dev.type == "cuda" and hasattr(be, "masked_stream") else None)
         self.pbuf, self.pgroup = [], []
@@ -180,6 +190,16 @@ class LockstepClassJob:
             for idx in self.cidx[:self.C]:
                 if torch.is_tensor(idx):
                     self._centre_plan(idx)
+        if (distinct_columns and hasattr(be, "knm_format") and be.knm_format(self.n_loc, self.M) in ("u24", "bf16")
+                and (distinct_columns == "force" or self.n_loc * self.M >= 2 ** 27)):
+            # which centres of a class repeat: host arithmetic on the job's inputs, like the ownership plan above, and the
+            # map's copy to the device — made for every class NOW, nothing of it waits for the GPU inside a step
+            for idx in self.cidx[:self.C]:
+                if torch.is_tensor(idx):
+                    cmap = _cols.column_map(idx)
+                    if cmap is not None:
+                        cmap.on(dev)
+                        self._cmaps[self._idx_key(idx)] = cmap
         if self.G > 1 and hasattr(be, "precond_batched") and hasattr(be, "lib") and dev.type == "cuda":
             # the two factor blocks and the chain's scratch at their final size now, not inside the first step that needs them
             # (a warm-up on a few classes runs smaller chains: the 22 GB scratch of a 6-class chain was first allocated in the
@@ -195,6 +215,18 @@ class LockstepClassJob:
         self.kbufs, self.pbuf, self.pgroup, self.scores, self.sbuf = [], [], [], None, None
 
     # ------------------------------------------------------------------ pieces
+    @staticmethod
+    def _idx_key(idx):
+        return (idx.data_ptr(), int(idx.numel()))
+
+    def _with_map(self, Zf, idx):
+        """The centres' Features, carrying the class's column map where it has one (backend.knm_rhs then stores the distinct
+        columns only; the preconditioner is built from all M centres either way)."""
+        cmap = self._cmaps.get(self._idx_key(idx)) if self._cmaps else None
+        if cmap is not None:
+            Zf.cmap = cmap
+        return Zf
+
     def _centre_plan(self, idx):
         """Who owns which centre row (every row of X has exactly one owner rank): per class, once, from the job's inputs —
         `mine` = local row ids of the centres this rank owns (in idx order), `cmax` = the largest count any rank owns (every
@@ -228,20 +260,20 @@ class LockstepClassJob:
         # measured); the ownership plan is host arithmetic on the job's inputs, made once per class
         be, X = self.be, self.X
         if self.world == 1:
-            return be.features(X.index_select(0, idx))
+            return self._with_map(be.features(X.index_select(0, idx)), idx)
         if getattr(self.shard, "emulated", False):
             # one rank of an emulated world: the (folded) indices all point at this rank's rows; the real rank would own M / W
             # of them and receive the rest — the gather runs locally, the collective is counted at its real size
             Z = X.index_select(0, idx - self.lo)
             self.shard._count("centre_gather", Z)
-            return be.features(Z)
+            return self._with_map(be.features(Z), idx)
         mine, cmax, slot, n_mine = self._centre_plan(idx)
         blk = torch.zeros((cmax, X.shape[1]), dtype=X.dtype, device=X.device)
         if n_mine:
             torch.index_select(X, 0, mine, out=blk[:n_mine])
         allb = torch.empty((self.world, cmax, X.shape[1]), dtype=X.dtype, device=X.device)
         self.shard.gather_blocks(blk, allb)
-        return be.features(allb.view(self.world * cmax, X.shape[1]).index_select(0, slot))
+        return self._with_map(be.features(allb.view(self.world * cmax, X.shape[1]).index_select(0, slot)), idx)
 
     def _score(self, ph, F, Z, K, alpha, c, summed=False):
         """scores[:, c] = K(X, Z) alpha.  summed: the fit has left K alpha in self.sbuf (f64, summed from the row products
@@ -358,6 +390,7 @@ class LockstepClassJob:
                                       shard=self.shard, owner=None, knm_out=self.kbufs[0],
                                       phase=(lambda name: phases[name]) if phases is not None else None,
                                       precond=P, precond_ready=(lambda ev=ev: _wait(ev)), knm_blocks=Ks, scores_out=self.sbuf)
+            self.trace.extend(("distinct", (c, K.M)) for K in Ks if getattr(K, "cmap", None) is not None)
             if alphas_out is not None:
                 alphas_out[c] = alpha
             self._score(ph, F, Z, Ks[0] if Ks else None, alpha, c,
@@ -418,6 +451,7 @@ class LockstepClassJob:
                 # issued behind this batch's CG in stream order: the factorisations then run beside the MFMA-bound scoring
                 # of this batch and K_nM build of the next, and the HBM-bound passes keep the chip to themselves
                 ready[bi + self.depth] = self._prepare(*sched[bi + self.depth], (bi + self.depth) % self.nslot, ph, infos)
+            self.trace.extend(("distinct", (c, K.M)) for c, K in zip(batch, Ks) if getattr(K, "cmap", None) is not None)
             if alphas_out is not None:
                 alphas_out.update((c, alphas[pos]) for pos, c in enumerate(batch))
             summed = self.sbuf is not None and len(batch) == 1 and len(Ks) == 1 and solver.scores_from_cg(be, Ks[0])

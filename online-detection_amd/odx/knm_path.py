@@ -10,7 +10,9 @@ odx_knm_fwdn_q, then odx_knm_bwdn_q, when ``wide_pass_min`` is set; on a streame
 vectors from one BUILD of K), the right-hand sides of several label columns from one read of the block (``ktwn``:
 odx_knm_bwdn_q) and the scores K alpha (``knm_mv``: odx_knm_mv); beside them the preconditioners of a lambda path
 (``precond_path``: odx_falkon_precond_path_f64) and the triangular products of several vectors from one read of a factor
-(``trmvn``: odx_trmvn_f64).
+(``trmvn``: odx_trmvn_f64).  A compact block that carries a column map (``Knm.cmap``: the distinct columns of a centre list with
+repeats, odx/cols.py) goes through ``ktk`` / ``ktk2`` / ``knm_mv`` with vectors of the list's length (odx_knm_fwd_bwd[2]_q_cols_t,
+odx_cols_fold_f64); the several-vector wrappers refuse it.
 
 What every wrapper repeats is stated once, in the helpers below: the arguments a block is passed as (``_qblock``,
 ``_fblock``), the workspace of an entry (``_pass_bytes``, ``_pass_ws``), the checks of a matrix of row vectors
@@ -35,6 +37,27 @@ def _compact(K):
 def _qblock(K):
     """The five arguments a compact-format entry (and odx_knm_mv, for every stored format) takes a block as."""
     return _p(K.K), K.ld, _p(K.lo), K.ld, hip.KNM_CODE[K.fmt]
+
+
+def _mapped(K):
+    """The ColumnMap of a block of distinct columns (backend.Knm.cmap), or None."""
+    return getattr(K, "cmap", None)
+
+
+def _vlen(K):
+    """The length of the vectors a pass over K takes and returns: the centre list's, K.M without a column map."""
+    return K.Mv if _mapped(K) is not None else K.M
+
+
+def _cols(K, device):
+    """The four trailing arguments of a _cols entry: Mv, col_of, start, pos."""
+    _, col_of, start, pos = K.cmap.on(device)
+    return K.Mv, _p(col_of), _p(start), _p(pos)
+
+
+def _no_map(who, K):
+    if _mapped(K) is not None:
+        raise ValueError("%s: not built for a block of distinct columns (a column map): ktk, ktk2 and knm_mv serve it" % who)
 
 
 def _fblock(K):
@@ -110,14 +133,19 @@ class PathOps:
         """out = K' (K v + w) over this shard (f64).  t_out: optional (n,) f64 that receives the row products K v (before w
         is added), a by-product of the same read of K (odx_knm_fwd_bwd[_q]_t); `out` is bitwise the same with or without it."""
         if out is None:
-            out = torch.empty(K.M, dtype=torch.float64, device=self.device)
+            out = torch.empty(_vlen(K), dtype=torch.float64, device=self.device)
         if t_out is not None:
             self._check_t_out(K, v, t_out)
         if K.fmt == "stream":
             self._ktk_stream(K, v, None, w, out, None)
             return out
         # (the _t entries with a null t_out ARE the plain entries: one function in C)
-        if _compact(K):
+        if _compact(K) and _mapped(K) is not None:
+            # distinct columns: v and out have the centre list's length, the block and its workspace K.M columns
+            ws = self._pass_ws("ktk", "odx_knm_fwd_bwd_q", K, hip.KNM_CODE[K.fmt])
+            self._call("odx_knm_fwd_bwd_q_cols_t", *_qblock(K), K.n, K.M, _p(v), _p(w), _p(out), _p(t_out), _p(ws), ws.numel(),
+                       *_cols(K, self.device))
+        elif _compact(K):
             ws = self._pass_ws("ktk", "odx_knm_fwd_bwd_q", K, hip.KNM_CODE[K.fmt])
             self._call("odx_knm_fwd_bwd_q_t", *_qblock(K), K.n, K.M, _p(v), _p(w), _p(out), _p(t_out), _p(ws), ws.numel())
         else:
@@ -132,7 +160,10 @@ class PathOps:
 
     def can_ktk2(self, K):
         """Whether the two-vector pass exists at this block's width (both vectors must fit in LDS: M <= 10 000).  A streamed
-        shard always has one: each chunk is built once and read for both vectors while it is resident."""
+        shard always has one: each chunk is built once and read for both vectors while it is resident.  A block of distinct
+        columns answers as the full block of its centre list would (every class of a job then decides alike)."""
+        if _mapped(K) is not None and self.lib.odx_knm_fwd_bwd2_q_workspace_bytes(max(K.n, 1), K.Mv, hip.KNM_CODE[K.fmt]) < 0:
+            return False
         return K.fmt == "stream" or self._ktk2_bytes(K) >= 0
 
     def ktk2(self, K, v1, v2, out1=None, out2=None, t_out=None):
@@ -141,14 +172,17 @@ class PathOps:
         if t_out is not None:
             self._check_t_out(K, v1, t_out)
         if out1 is None:
-            out1 = torch.empty(K.M, dtype=torch.float64, device=self.device)
+            out1 = torch.empty(_vlen(K), dtype=torch.float64, device=self.device)
         if out2 is None:
-            out2 = torch.empty(K.M, dtype=torch.float64, device=self.device)
+            out2 = torch.empty(_vlen(K), dtype=torch.float64, device=self.device)
         if K.fmt == "stream":
             self._ktk_stream(K, v1, v2, None, out1, out2)
             return out1, out2
         vecs = (_p(v1), _p(v2), _p(out1), _p(out2), _p(t_out))
-        if _compact(K):
+        if _compact(K) and _mapped(K) is not None:
+            ws = self._pass_ws("ktk", "odx_knm_fwd_bwd2_q", K, hip.KNM_CODE[K.fmt])
+            self._call("odx_knm_fwd_bwd2_q_cols_t", *_qblock(K), K.n, K.M, *vecs, _p(ws), ws.numel(), *_cols(K, self.device))
+        elif _compact(K):
             ws = self._pass_ws("ktk", "odx_knm_fwd_bwd2_q", K, hip.KNM_CODE[K.fmt])
             self._call("odx_knm_fwd_bwd2_q_t", *_qblock(K), K.n, K.M, *vecs, _p(ws), ws.numel())
         else:
@@ -224,6 +258,7 @@ class PathOps:
         (the entry is not built for them)."""
         if not _compact(K):
             raise ValueError("kvn: compact stored blocks only (u24 / bf16), got %r" % (K.fmt,))
+        _no_map("kvn", K)
         L, M, n = V.shape[0], K.M, K.n
         if out is None:
             out = torch.zeros((L, (n + 1) // 2 * 2), dtype=torch.float64, device=self.device)
@@ -251,6 +286,7 @@ class PathOps:
         groups of ktkn_span(K) = 16 rows, each from ONE build of K (odx_gauss_ktk_stream_h2n; a single row goes through
         ktk).  Columns [0, K.M) of V / out are used; rows must be 16-byte aligned for groups of 3 or more (on a streamed
         shard: of 2 or more)."""
+        _no_map("ktkn", K)
         L, M = V.shape[0], K.M
         if out is None:
             out = torch.zeros((L, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
@@ -284,6 +320,7 @@ class PathOps:
         of one goes through ktk(K, w=...).  f32 blocks (small, not HBM-bound: ktkn's decision) loop ktk(K, w=...), and so do
         streamed shards — there every row is one recompute of K: a build-once entry for several weight vectors is NOT
         built.  Rows of W and out must be 16-byte aligned for groups of 2 or more."""
+        _no_map("ktwn", K)
         T, M, n = W.shape[0], K.M, K.n
         if out is None:
             out = torch.zeros((T, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
@@ -331,8 +368,14 @@ class PathOps:
                 out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
             return self.cg_scores_store(summed, out)
         alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
-        if alpha.numel() != K.M:
-            raise ValueError("knm_mv: alpha has %d entries but the block has %d columns" % (alpha.numel(), K.M))
+        if alpha.numel() != _vlen(K):
+            raise ValueError("knm_mv: alpha has %d entries but the block has %d columns" % (alpha.numel(), _vlen(K)))
+        if _mapped(K) is not None:
+            # distinct columns: K_full alpha = K fold(alpha)
+            _, start, pos = _cols(K, self.device)[1:]
+            folded = torch.empty(K.M, dtype=torch.float64, device=self.device)
+            self._call("odx_cols_fold_f64", _p(alpha), K.Mv, start, pos, K.M, _p(folded))
+            alpha = folded
         if out is None:
             out = torch.empty((K.n, 1), dtype=torch.float32, device=self.device)
         if out.dtype != torch.float32 or out.shape[0] != K.n or (out.dim() == 2 and out.shape[1] != 1):

@@ -320,8 +320,10 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     one_call = shard is None and allreduce is None and phase is None and hasattr(be, "cg_solve") and not acc
     if one_call and getattr(K, "fmt", "f32") != "f32":
         # compact-format block: the class-batched library loop with a batch of one (odx_falkon_cg_batched_q_f64), where the
-        # block's pass configuration has one and the factors are one contiguous block
+        # block's pass configuration has one and the factors are one contiguous block (and the block holds every column of
+        # the centre list: the library loop knows no column map)
         one_call = bool(hasattr(be, "cg_batched_supported") and getattr(P, "block_rows", None) is not None
+                        and getattr(K, "cmap", None) is None
                         and be.cg_batched_supported([K.n], [K.M], K.fmt))
     if one_call:
         # one shard, nothing to time per kernel family: the schedule of _cg_run as one library call (odx_falkon_cg_f64)
