@@ -49,6 +49,12 @@ int odx_device_cus(void);
  *                                                                     route (otherwise only D % 8 != 0 takes it)
  *   "rls_force_inverse_solve" 0 | 1                          0        TEST HOOK: every RLS solve by the explicit inverse
  *                                                                     (otherwise only D + 1 > 2048 takes it)
+ *   "t_inverse_unmerged"      0 | 1 | 2                      2        top merge levels of T's inverse a lock-step job of more than
+ *                                                                     8192 centres leaves unmerged (levels of 4096 rows and more
+ *                                                                     only; odx/job.py holds the rule, the library only keeps the
+ *                                                                     value).  Measured at the headline shape: 0 / 1 / 2 = 5278 /
+ *                                                                     5248 / 5162 ms per step (profiles/build_phase.md)
+ *   "t_inverse_force_stop"    0 | 128 2^k                    0        TEST HOOK: that stop level for every lock-step job
  *
  * odx_set_option: ODX_ERR_INVALID for an unknown name or a value outside the column above.  odx_option_default: the default. */
 int odx_set_option(const char* name, int value);
@@ -403,12 +409,29 @@ int odx_falkon_precond_batched_f64(const float* const* Z, const int64_t* ldz, co
                                    int64_t Mmax, int D, double sigma, double lam, double eps,
                                    double* out, int64_t ld, int64_t out_stride, int32_t* info,
                                    void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* The same call with a PARTIAL inverse of T: the merge levels of t_stop rows (128 2^k) and more are not run
+ * (odx_trtri_partial_f64); LTi / LTit come out blocked and are multiplied by odx_tri_blocked_mv_f64 only.  LAi / LAit are the
+ * full inverses.  t_stop = 0: odx_falkon_precond_batched_f64. */
+int odx_falkon_precond_batched_partial_f64(const float* const* Z, const int64_t* ldz, const int64_t* M, int B,
+                                           int64_t Mmax, int D, double sigma, double lam, double eps, int64_t t_stop,
+                                           double* out, int64_t ld, int64_t out_stride, int32_t* info,
+                                           void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 /* y = op(Tri) x for a triangular M x M f64 matrix, rows as dot products.
  * uplo: 0 = lower (uses columns j <= i), 1 = upper (j >= i).
  * y = alpha * Tri x + beta * z  (z may be NULL when beta == 0; y may alias z).          */
 int odx_trmv_f64(const double* Tri, int64_t ld, int64_t M, int uplo, const double* x,
                  double alpha, double beta, const double* z, double* y, odx_stream_t stream);
+
+/* y = alpha * B x + beta * z for a BLOCKED inverse B as odx_trtri_partial_f64 leaves it: Tri holds the inverted diagonal blocks
+ * [bounds[b], bounds[b + 1]) and, between them, the factor's own blocks.  uplo 0: Tri = Li, B = L^-1 (forward substitution over
+ * the blocks); 1: Tri = Lit, B = L^-T (backward).  bounds: HOST array of nblocks + 1 ascending values from 0 to M, the interior
+ * ones even.  2 nblocks - 1 launches, one wave per row with odx_trmv_f64's loads and order of additions; one block is
+ * odx_trmv_f64 bit for bit.  workspace: odx_tri_blocked_mv_workspace_bytes(M), 16-byte aligned.  y may alias z but not x. */
+int64_t odx_tri_blocked_mv_workspace_bytes(int64_t M);
+int odx_tri_blocked_mv_f64(const double* Tri, int64_t ld, int64_t M, int uplo, const int64_t* bounds, int nblocks,
+                           const double* x, double alpha, double beta, const double* z, double* y,
+                           void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 /* Y[q] = alpha * Tri X[q] + beta * Z[q] for q < nv, 1 <= nv <= 8, from ONE read of the factor (the states of a multi-output
  * fit share one preconditioner).  X / Z / Y: nv f64 rows, ldx / ldz / ldy doubles apart; X rows 16-byte aligned, ldx even.
@@ -505,6 +528,11 @@ int odx_potrf_f64(double* A, int64_t lda, int64_t M, int32_t* info, void* worksp
 int64_t odx_trtri_workspace_bytes(int64_t M);
 int odx_trtri_f64(const double* L, int64_t ldl, int64_t M, double* Li, double* Lit, int64_t ld,
                   void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* A partial inverse: the merge levels of `stop` rows (128 2^k) and more are not run.  The diagonal blocks of `stop` rows are
+ * the full call's, bit for bit; below them Li holds L's own blocks and Lit, above them, their transposes.  stop = 0 or
+ * stop >= M: odx_trtri_f64.  Workspace as odx_trtri_f64. */
+int odx_trtri_partial_f64(const double* L, int64_t ldl, int64_t M, int64_t stop, double* Li, double* Lit, int64_t ld,
+                          void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 int odx_convert_f32_f64(const float* src, int64_t lds, double* dst, int64_t ldd, int64_t rows,
                         int64_t cols, odx_stream_t stream);
 int odx_convert_f64_f32(const double* src, int64_t lds, float* dst, int64_t ldd, int64_t rows,

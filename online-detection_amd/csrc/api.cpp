@@ -24,10 +24,11 @@ struct OptSpec {
   const char* name;
   int def, lo, hi;      // default, inclusive range (h2_tile: the three legal values are checked separately)
 };
+constexpr int T_INVERSE_UNMERGED_DEFAULT = 2;      // the headline shape's measurement: profiles/build_phase.md
 static const OptSpec g_opt_spec[OPT_COUNT] = {
     {"h2_tile", 0, 0, 256}, {"precond", 0, 0, 2}, {"chain_helpers", -1, -1, 1}, {"rls_force_nt_gram", 0, 0, 1},
-    {"rls_force_inverse_solve", 0, 0, 1}};
-static int g_opt[OPT_COUNT] = {0, 0, -1, 0, 0};
+    {"rls_force_inverse_solve", 0, 0, 1}, {"t_inverse_unmerged", T_INVERSE_UNMERGED_DEFAULT, 0, 2}, {"t_inverse_force_stop", 0, 0, 1 << 20}};
+static int g_opt[OPT_COUNT] = {0, 0, -1, 0, 0, T_INVERSE_UNMERGED_DEFAULT, 0};
 int lib_option(int which) { return g_opt[which]; }
 static int opt_index(const char* name) {
   if (name)

@@ -453,17 +453,38 @@ __global__ __launch_bounds__(256) void place_diag_inverses_kernel(const double* 
   }
 }
 
-// y[i] = alpha * sum_{j in tri range} Tri[i][j] x[j] + beta * z[i]; one wave per row, 16-byte loads, four of them in
-// flight per lane (four partial sums) over the aligned pairs of the row's range; the odd elements at its ends go to lane 0.
-__device__ __forceinline__ void trmv_row(const double* __restrict__ Tri, int64_t ld, int64_t M, int uplo,
-                                         const double* __restrict__ x, double alpha, double beta,
-                                         const double* __restrict__ z, double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= M) return;
-  if (!uplo) i = M - 1 - i;      // longest rows first: a lower factor's long rows, dispatched last, were the launch's tail
-  const int64_t jlo = uplo ? i : 0, jhi = uplo ? M : i + 1;  // [jlo, jhi)
-  const double* row = Tri + i * ld;
+// A partial inverse's blocks below the block diagonal (blocks of `stop` rows, a multiple of 32): Li <- L, Lit <- L'
+__global__ __launch_bounds__(256) void place_factor_blocks_kernel(const double* __restrict__ L, int64_t ldl, int64_t M,
+                                                                  int64_t stop, double* __restrict__ Li,
+                                                                  double* __restrict__ Lit, int64_t ld, int64_t zstrideA,
+                                                                  int64_t zstrideO) {
+  __shared__ double tile[32][33];
+  const int64_t r0 = stop + (int64_t)blockIdx.y * 32, c0 = (int64_t)blockIdx.x * 32;
+  if (c0 >= r0 / stop * stop) return;          // (the whole workgroup: a 32 x 32 tile lies inside one block)
+  L += (int64_t)blockIdx.z * zstrideA;
+  Li += (int64_t)blockIdx.z * zstrideO;
+  Lit += (int64_t)blockIdx.z * zstrideO;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t r = r0 + ty + q * 8, c = c0 + tx;
+    const double v = r < M ? L[r * ldl + c] : 0.0;
+    tile[ty + q * 8][tx] = v;
+    if (r < M) Li[r * ld + c] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t r = c0 + ty + q * 8, c = r0 + tx;
+    if (c < M) Lit[r * ld + c] = tile[tx][ty + q * 8];
+  }
+}
+
+// sum_{j in [jlo, jhi)} row[j] x[j], the total in every lane: one wave per row, 16-byte loads, four of them in flight per lane
+// (four partial sums) over the aligned pairs of the range; the odd elements at its ends go to lane 0.  row and x are 16-byte
+// aligned at index 0.  The order of additions is fixed.
+__device__ __forceinline__ double row_dot(const double* __restrict__ row, const double* __restrict__ x, int64_t jlo, int64_t jhi,
+                                          int lane) {
   const int64_t q0 = (jlo + 1) >> 1, q1 = jhi >> 1;           // whole pairs [2 q0, 2 q1); ld is even so pairs are 16-B aligned
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
   if (lane == 0) {
@@ -489,10 +510,24 @@ __device__ __forceinline__ void trmv_row(const double* __restrict__ Tri, int64_t
   double s = (s0 + s1) + (s2 + s3);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  return s;
+}
+
+// y[i] = alpha * sum_{j in tri range} Tri[i][j] x[j] + beta * z[i], by row_dot.  yraw != nullptr: the sum itself goes there too
+// (a blocked product's later steps need it unscaled: tri_blocked_mv_f64).
+__device__ __forceinline__ void trmv_row(const double* __restrict__ Tri, int64_t ld, int64_t M, int uplo,
+                                         const double* __restrict__ x, double alpha, double beta,
+                                         const double* __restrict__ z, double* __restrict__ y, double* __restrict__ yraw = nullptr) {
+  const int lane = threadIdx.x & 63;
+  int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= M) return;
+  if (!uplo) i = M - 1 - i;      // longest rows first: a lower factor's long rows, dispatched last, were the launch's tail
+  const double s = row_dot(Tri + i * ld, x, uplo ? i : 0, uplo ? M : i + 1, lane);
   if (lane == 0) {
     double r = alpha * s;
     if (beta != 0.0) r += beta * z[i];
     y[i] = r;
+    if (yraw) yraw[i] = s;
   }
 }
 
@@ -501,6 +536,26 @@ __global__ __launch_bounds__(256) void trmv_f64_kernel(const double* __restrict_
                                                        double beta, const double* __restrict__ z,
                                                        double* __restrict__ y) {
   trmv_row(Tri, ld, M, uplo, x, alpha, beta, z, y);
+}
+
+// One diagonal block of a blocked product (tri_blocked_mv_f64): trmv_f64_kernel's rows, and the unscaled sums to yraw.
+__global__ __launch_bounds__(256) void trmv_block_f64_kernel(const double* __restrict__ Tri, int64_t ld, int64_t M,
+                                                             int uplo, const double* __restrict__ x, double alpha,
+                                                             double beta, const double* __restrict__ z,
+                                                             double* __restrict__ y, double* __restrict__ yraw) {
+  trmv_row(Tri, ld, M, uplo, x, alpha, beta, z, y, yraw);
+}
+
+// u[i] = x[i] - sum_{j in [c0, c1)} A[i][j] t[j] for the rows [r0, r1): the rectangular step of a blocked product, one wave
+// per row by row_dot (the loads and the order of additions of trmv_row).  c0 is even.
+__global__ __launch_bounds__(256) void rect_dot_f64_kernel(const double* __restrict__ A, int64_t ld, int64_t r0, int64_t r1,
+                                                           int64_t c0, int64_t c1, const double* __restrict__ t,
+                                                           const double* __restrict__ x, double* __restrict__ u) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= r1) return;
+  const double s = row_dot(A + i * ld, t, c0, c1, lane);
+  if (lane == 0) u[i] = x[i] - s;
 }
 
 // Y[q][i] = alpha * sum_{j in tri range} Tri[i][j] X[q][j] + beta * Z[q][i] for q < nv <= NV vectors from ONE read of the
@@ -918,11 +973,16 @@ int trmv_batched_f64(const double* Tri, int64_t ld, int64_t tri_stride, int uplo
 // pk != nullptr: the merge levels of 512 rows and more run on the split-f16 tile core (the inverse of a factor that only
 // preconditions): pk holds pk_cap 4-byte units per matrix (matrices pk_z apart; a level needs at most 2 M roundup(M, 64));
 // bound_l / bound_inv: bounds of |L_ij| and of |(L^-1)_ij| the operand scales are taken from.
+// stop > 0 (NB 2^k): a PARTIAL inverse.  The merge levels s >= stop are not run: the diagonal blocks of `stop` rows hold what
+// the full call has there (they are final after level stop / 2), and below them Li holds L itself, Lit its transpose — the
+// blocked form tri_blocked_mv_f64 multiplies by.
 int trtri_from_diag_f64(const double* L, int64_t ldl, int64_t M, const double* Dinv, double* Li, double* Lit,
                         int64_t ld, double* WT, hipStream_t stream, const ZBatch& zb, uint32_t* pk, int64_t pk_cap, int64_t pk_z,
-                        double bound_l, double bound_inv) {
+                        double bound_l, double bound_inv, int64_t stop) {
   constexpr int NB = POTRF_NB;
   ODX_REQUIRE(ld % 2 == 0 && ldl % 2 == 0, "trtri_f64: leading dimensions must be even");
+  ODX_REQUIRE(stop == 0 || (stop >= NB && stop % NB == 0 && (stop / NB & (stop / NB - 1)) == 0),
+              "trtri_f64: the stop level must be %d 2^k", NB);
   const int Z = zb.count;
   ODX_REQUIRE(Z >= 1 && Z <= ODX_MAX_ZBATCH && zb.strideA % 2 == 0 && zb.strideO % 2 == 0 && zb.strideW % 2 == 0,
               "trtri_f64: class batch of 1..%d matrices, even strides", ODX_MAX_ZBATCH);
@@ -931,6 +991,12 @@ int trtri_from_diag_f64(const double* L, int64_t ldl, int64_t M, const double* D
                      Li, Lit, ld, zb.strideD, zb.strideO);
   ODX_CHECK_LAUNCH("place_diag_inverses");
   for (int64_t s = NB; s < M; s *= 2) {
+    if (stop > 0 && s >= stop) {
+      hipLaunchKernelGGL(place_factor_blocks_kernel, dim3((unsigned)ceil_div(M, 32), (unsigned)ceil_div(M - stop, 32), (unsigned)Z),
+                         dim3(256), 0, stream, L, ldl, M, stop, Li, Lit, ld, zb.strideA, zb.strideO);
+      ODX_CHECK_LAUNCH("place_factor_blocks");
+      break;
+    }
     const int nb = (int)ceil_div(M, 2 * s);  // pairs; the last may be ragged or empty
     const int nbe = (int)ceil_div(M - s, 2 * s);                       // pairs with rows below their first block
     const int64_t m2l = M - s - (int64_t)(nbe - 1) * 2 * s;            // rows of the last pair's second block (<= s)
@@ -1092,13 +1158,13 @@ extern "C" int64_t odx_trtri_workspace_bytes(int64_t M) {
   return odx_potrf_workspace_bytes(M) + M * M * (int64_t)sizeof(double);
 }
 
-extern "C" int odx_trtri_f64(const double* L, int64_t ldl, int64_t M, double* Li, double* Lit, int64_t ld,
-                             void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+static int trtri_f64_impl(const char* who, const double* L, int64_t ldl, int64_t M, int64_t stop, double* Li, double* Lit,
+                          int64_t ld, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
   if (M <= 0) return ODX_OK;
-  ODX_REQUIRE(L && Li && Lit && workspace, "odx_trtri_f64: null pointer");
-  ODX_REQUIRE(ld >= M && ldl >= M && aligned16(L) && aligned16(Li) && aligned16(Lit), "odx_trtri_f64: bad ld / alignment");
+  ODX_REQUIRE(L && Li && Lit && workspace, "%s: null pointer", who);
+  ODX_REQUIRE(ld >= M && ldl >= M && aligned16(L) && aligned16(Li) && aligned16(Lit), "%s: bad ld / alignment", who);
   if (workspace_bytes < odx_trtri_workspace_bytes(M)) {
-    set_error("odx_trtri_f64: workspace too small");
+    set_error("%s: workspace too small", who);
     return ODX_ERR_WORKSPACE;
   }
   hipStream_t s = as_stream(stream);
@@ -1109,7 +1175,56 @@ extern "C" int odx_trtri_f64(const double* L, int64_t ldl, int64_t M, double* Li
   ODX_CHECK_LAUNCH("trtri_diag");
   ODX_PROPAGATE(fill_f64(Li, ld, M, M, 0.0, s));
   ODX_PROPAGATE(fill_f64(Lit, ld, M, M, 0.0, s));
-  return trtri_from_diag_f64(L, ldl, M, Dinv, Li, Lit, ld, WT, s);
+  return trtri_from_diag_f64(L, ldl, M, Dinv, Li, Lit, ld, WT, s, ZBatch(), nullptr, 0, 0, 1.0, 1.0, stop);
+}
+
+extern "C" int odx_trtri_f64(const double* L, int64_t ldl, int64_t M, double* Li, double* Lit, int64_t ld,
+                             void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  return trtri_f64_impl("odx_trtri_f64", L, ldl, M, 0, Li, Lit, ld, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_trtri_partial_f64(const double* L, int64_t ldl, int64_t M, int64_t stop, double* Li, double* Lit, int64_t ld,
+                                     void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  return trtri_f64_impl("odx_trtri_partial_f64", L, ldl, M, stop, Li, Lit, ld, workspace, workspace_bytes, stream);
+}
+
+// workspace: t | u, the unscaled result and the right-hand side of the block being solved (round_up(M, 2) doubles each)
+extern "C" int64_t odx_tri_blocked_mv_workspace_bytes(int64_t M) {
+  return M <= 0 ? 0 : 2 * round_up(M, 2) * (int64_t)sizeof(double);
+}
+
+extern "C" int odx_tri_blocked_mv_f64(const double* Tri, int64_t ld, int64_t M, int uplo, const int64_t* bounds, int nblocks,
+                                      const double* x, double alpha, double beta, const double* z, double* y, void* workspace,
+                                      int64_t workspace_bytes, odx_stream_t stream) {
+  if (M <= 0) return ODX_OK;
+  ODX_REQUIRE(Tri && x && y && bounds && workspace && (beta == 0.0 || z), "odx_tri_blocked_mv_f64: null pointer");
+  ODX_REQUIRE(ld % 2 == 0 && ld >= M && aligned16(Tri) && aligned16(x) && aligned16(workspace),
+              "odx_tri_blocked_mv_f64: Tri/x/workspace must be 16-byte aligned, ld even, ld >= M");
+  ODX_REQUIRE(x != y, "odx_tri_blocked_mv_f64: x and y must not alias");
+  ODX_REQUIRE(nblocks >= 1 && bounds[0] == 0 && bounds[nblocks] == M, "odx_tri_blocked_mv_f64: bounds must run from 0 to M");
+  for (int b = 0; b < nblocks; ++b)
+    ODX_REQUIRE(bounds[b] < bounds[b + 1] && bounds[b] % 2 == 0, "odx_tri_blocked_mv_f64: bounds must ascend, interior ones even");
+  if (workspace_bytes < odx_tri_blocked_mv_workspace_bytes(M)) {
+    set_error("odx_tri_blocked_mv_f64: workspace too small");
+    return ODX_ERR_WORKSPACE;
+  }
+  hipStream_t s = as_stream(stream);
+  double* t = static_cast<double*>(workspace);
+  double* u = t + round_up(M, 2);
+  // lower: forward substitution over the blocks (u_i = x_i - L[i, < i] t, t_i = X_ii u_i); upper: backward over Lit
+  for (int k = 0; k < nblocks; ++k) {
+    const int b = uplo ? nblocks - 1 - k : k;
+    const int64_t r0 = bounds[b], r1 = bounds[b + 1];
+    if (k > 0) {
+      hipLaunchKernelGGL(rect_dot_f64_kernel, dim3((unsigned)ceil_div(r1 - r0, 4)), dim3(256), 0, s, Tri, ld, r0, r1,
+                         uplo ? r1 : (int64_t)0, uplo ? M : r0, t, x, u);
+      ODX_CHECK_LAUNCH("odx_tri_blocked_mv_f64 (rect)");
+    }
+    hipLaunchKernelGGL(trmv_block_f64_kernel, dim3((unsigned)ceil_div(r1 - r0, 4)), dim3(256), 0, s, Tri + r0 * (ld + 1), ld,
+                       r1 - r0, uplo, (k > 0 ? u : x) + r0, alpha, beta, z ? z + r0 : nullptr, y + r0, t + r0);
+    ODX_CHECK_LAUNCH("odx_tri_blocked_mv_f64 (block)");
+  }
+  return ODX_OK;
 }
 
 // ---------------------------------------------------------------- FALKON preconditioner
@@ -1279,7 +1394,7 @@ extern "C" int64_t odx_falkon_precond_batched_workspace_bytes(int64_t Mmax, int 
 }
 
 static int falkon_precond_batched_f64_impl(const float* const* Z, const int64_t* ldz, const int64_t* M, int B,
-                                           int64_t Mmax, int D, double sigma, double lam, double eps, double* out,
+                                           int64_t Mmax, int D, double sigma, double lam, double eps, int64_t t_stop, double* out,
                                            int64_t ld, int64_t out_stride, int32_t* info, void* workspace,
                                            int64_t workspace_bytes, odx_stream_t stream);
 
@@ -1287,12 +1402,20 @@ extern "C" int odx_falkon_precond_batched_f64(const float* const* Z, const int64
                                               int64_t Mmax, int D, double sigma, double lam, double eps, double* out,
                                               int64_t ld, int64_t out_stride, int32_t* info, void* workspace,
                                               int64_t workspace_bytes, odx_stream_t stream) {
-  const int rc = falkon_precond_batched_f64_impl(Z, ldz, M, B, Mmax, D, sigma, lam, eps, out, ld, out_stride, info, workspace, workspace_bytes, stream);
+  const int rc = falkon_precond_batched_f64_impl(Z, ldz, M, B, Mmax, D, sigma, lam, eps, 0, out, ld, out_stride, info, workspace, workspace_bytes, stream);
   return rc;
 }
 
+extern "C" int odx_falkon_precond_batched_partial_f64(const float* const* Z, const int64_t* ldz, const int64_t* M, int B,
+                                                      int64_t Mmax, int D, double sigma, double lam, double eps, int64_t t_stop,
+                                                      double* out, int64_t ld, int64_t out_stride, int32_t* info, void* workspace,
+                                                      int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(t_stop >= 0, "odx_falkon_precond_batched_partial_f64: negative stop level");
+  return falkon_precond_batched_f64_impl(Z, ldz, M, B, Mmax, D, sigma, lam, eps, t_stop, out, ld, out_stride, info, workspace, workspace_bytes, stream);
+}
+
 static int falkon_precond_batched_f64_impl(const float* const* Z, const int64_t* ldz, const int64_t* M, int B,
-                                           int64_t Mmax, int D, double sigma, double lam, double eps, double* out,
+                                           int64_t Mmax, int D, double sigma, double lam, double eps, int64_t t_stop, double* out,
                                            int64_t ld, int64_t out_stride, int32_t* info, void* workspace,
                                            int64_t workspace_bytes, odx_stream_t stream) {
   ODX_REQUIRE(B >= 1 && B <= ODX_MAX_ZBATCH, "odx_falkon_precond_batched_f64: 1 <= B <= %d classes per call", ODX_MAX_ZBATCH);
@@ -1354,7 +1477,7 @@ static int falkon_precond_batched_f64_impl(const float* const* Z, const int64_t*
   // fork: inverses of all L_T on the side stream (scratch W3)
   ODX_CHECK_HIP(hipEventRecord(side->fork, s));
   ODX_CHECK_HIP(hipStreamWaitEvent(s2, side->fork, 0));
-  ODX_PROPAGATE(trtri_from_diag_f64(W0, wld, Mmax, DinvT, LTi, LTit, ld, W3, s2, zt));
+  ODX_PROPAGATE(trtri_from_diag_f64(W0, wld, Mmax, DinvT, LTi, LTit, ld, W3, s2, zt, nullptr, 0, 0, 1.0, 1.0, t_stop));
   ODX_CHECK_HIP(hipEventRecord(side->join, s2));
   // main: W1 = L_T' = T; W2 = T T' / M_b + lam I; L_A in place in W2
   ODX_PROPAGATE(transpose_f64(W0, wld, W1, wld, Mmax, Mmax, s, B, wsz, wsz));

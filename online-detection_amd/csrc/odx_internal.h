@@ -11,6 +11,8 @@ enum LibOpt {
   OPT_CHAIN_HELPERS,               // -1 automatic (helper streams from 4096 centres on) | 0 never | 1 always
   OPT_RLS_FORCE_NT_GRAM,           // test hook: 1 = the transposed-copy + NT-GEMM Gram (the route of D % 8 != 0) for every D
   OPT_RLS_FORCE_INVERSE_SOLVE,     // test hook: 1 = the explicit-inverse solve (the route of D + 1 > 16 x 128) for every D
+  OPT_T_INVERSE_UNMERGED,          // 0 | 1 | 2: top merge levels of T's inverse a lock-step job leaves unmerged (the host's rule reads it)
+  OPT_T_INVERSE_FORCE_STOP,        // test hook: > 0 = that stop level for every lock-step job, whatever its size
   OPT_COUNT
 };
 int lib_option(int which);
@@ -66,7 +68,7 @@ int potrf_f64(double* A, int64_t lda, int64_t M, double* Dinv /* nblk x NB x NB 
               float pk_scale = 1.f);
 int trtri_from_diag_f64(const double* L, int64_t ldl, int64_t M, const double* Dinv, double* Li, double* Lit,
                         int64_t ld, double* WT, hipStream_t stream, const ZBatch& zb = ZBatch(), uint32_t* pk = nullptr,
-                        int64_t pk_cap = 0, int64_t pk_z = 0, double bound_l = 1.0, double bound_inv = 1.0);
+                        int64_t pk_cap = 0, int64_t pk_z = 0, double bound_l = 1.0, double bound_inv = 1.0, int64_t stop = 0);
 int transpose_f64(const double* src, int64_t lds, double* dst, int64_t ldd, int64_t rows, int64_t cols,
                   hipStream_t stream, int zcount = 1, int64_t zstride_src = 0, int64_t zstride_dst = 0);
 int add_diag_f64(double* A, int64_t lda, int64_t M, double value, hipStream_t stream, int zcount = 1, int64_t zstride = 0);

@@ -62,8 +62,19 @@ class PackedRows:
 
 
 class Precond:
-    """Inverse Cholesky factors of the FALKON preconditioner, f64, row-major (M x ld)."""
-    __slots__ = ("LTi", "LTit", "LAi", "LAit", "M", "ld", "info", "block_rows")
+    """Inverse Cholesky factors of the FALKON preconditioner, f64, row-major (M x ld).  blocks: () for fully merged inverses;
+    otherwise LTi / LTit are a PARTIAL inverse of T (odx_trtri_partial_f64) and blocks holds its block boundaries 0 < ... < M.
+    Only HipBackend.trmv multiplies by such a pair; every other consumer of a Precond refuses it (require_merged)."""
+    __slots__ = ("LTi", "LTit", "LAi", "LAit", "M", "ld", "info", "block_rows", "blocks")
+
+    def __init__(self):
+        self.blocks = ()
+
+
+def require_merged(P, who):
+    """A consumer that reads LTi / LTit as whole triangular matrices: a partial inverse is an error there, never a wrong result."""
+    if getattr(P, "blocks", ()):
+        raise ValueError("%s: this preconditioner holds a partial inverse of T (blocks %r); only trmv multiplies by it" % (who, P.blocks))
 
 
 class Knm:
@@ -367,11 +378,14 @@ class HipBackend(PathOps):
 
     MAX_CLASS_BATCH = 32        # ODX_MAX_ZBATCH of libodx
 
-    def precond_batched(self, Zfs, sigma, lam, eps, out=None, ws_key="precond_batched", Mmax=None):
+    def precond_batched(self, Zfs, sigma, lam, eps, out=None, ws_key="precond_batched", Mmax=None, t_stop=0):
         """The preconditioners of len(Zfs) <= 32 independent classes with ONE chain of launches
         (odx_falkon_precond_batched_f64): returns one Precond per class, views into a shared (B, 4, Mmax, ld) f64 block
         (`out` when given) whose leading M_b x M_b blocks equal, bit for bit, what precond() makes for that class.  Mmax: rows
-        of a class's slot when that is more than this call's largest class (two calls filling halves of one block)."""
+        of a class's slot when that is more than this call's largest class (two calls filling halves of one block).
+        t_stop > 0: T's inverse stays partial, its merge levels of t_stop rows and more are not run
+        (odx_falkon_precond_batched_partial_f64); a class with more than t_stop centres then carries its block boundaries in
+        Precond.blocks, and its LTi / LTit are for trmv alone."""
         B = len(Zfs)
         if not 1 <= B <= self.MAX_CLASS_BATCH:
             raise ValueError("precond_batched: 1..%d classes per call, got %d" % (self.MAX_CLASS_BATCH, B))
@@ -392,9 +406,15 @@ class HipBackend(PathOps):
         zp = (ctypes.c_void_p * B)(*[z.X.data_ptr() for z in Zfs])
         zl = (ctypes.c_int64 * B)(*[int(z.ld) for z in Zfs])
         zm = (ctypes.c_int64 * B)(*Ms)
-        hip.check(self.lib.odx_falkon_precond_batched_f64(zp, zl, zm, B, Mmax, D, float(sigma), float(lam), float(eps), _p(out), ld,
-                                                          4 * Mmax * ld, _p(info), _p(ws), ws.numel(), self._stream()),
-                  "odx_falkon_precond_batched_f64")
+        t_stop = int(t_stop) if int(t_stop) < Mmax else 0
+        if t_stop:
+            hip.check(self.lib.odx_falkon_precond_batched_partial_f64(zp, zl, zm, B, Mmax, D, float(sigma), float(lam), float(eps), t_stop,
+                                                                      _p(out), ld, 4 * Mmax * ld, _p(info), _p(ws), ws.numel(),
+                                                                      self._stream()), "odx_falkon_precond_batched_partial_f64")
+        else:
+            hip.check(self.lib.odx_falkon_precond_batched_f64(zp, zl, zm, B, Mmax, D, float(sigma), float(lam), float(eps), _p(out), ld,
+                                                              4 * Mmax * ld, _p(info), _p(ws), ws.numel(), self._stream()),
+                      "odx_falkon_precond_batched_f64")
         Ps = []
         for b, M in enumerate(Ms):
             P = Precond()
@@ -402,6 +422,8 @@ class HipBackend(PathOps):
             P.LTi, P.LTit, P.LAi, P.LAit = (out[b, k, :M] for k in range(4))
             P.info = info[b:b + 1]
             P.block_rows = Mmax                  # rows of each factor's slot in the shared block (cg_solve_batched)
+            if t_stop and M > t_stop:
+                P.blocks = tuple(range(0, M, t_stop)) + (M,)
             Ps.append(P)
         return Ps
 
@@ -581,6 +603,7 @@ class HipBackend(PathOps):
     def cg_solve(self, K, P, b0, n_total, lam, maxiter, opt):
         """The CG loop of an unsharded fit in one library call (odx_falkon_cg_f64); returns alpha (M,) f64.  f32-stored
         blocks only: the library loop streams K as floats (compact formats go through solver.falkon_fit's loop)."""
+        require_merged(P, "cg_solve")
         if K.fmt != "f32":
             raise hip.OdxError("cg_solve: the one-call CG loop needs an f32-stored K_nM block, got %r" % K.fmt)
         alpha = torch.empty(K.M, dtype=torch.float64, device=self.device)
@@ -613,6 +636,8 @@ class HipBackend(PathOps):
         bit what cg_solve gives — or None when the classes do not share a pass configuration / storage format.  Blocks in
         a compact format (24-bit fixed point, bf16) go through odx_falkon_cg_batched_q_f64."""
         B = len(Ks)
+        for P in Ps:
+            require_merged(P, "cg_solve_batched")
         fmt = Ks[0].fmt
         if fmt == "stream" or any(k.fmt != fmt for k in Ks):     # one stored format per batch
             return None
@@ -649,11 +674,22 @@ class HipBackend(PathOps):
         return alpha
 
     _TRI = {"LTi": 0, "LTit": 1, "LAi": 0, "LAit": 1}
+    _bounds = {}                # block boundaries of partial inverses as the HOST arrays odx_tri_blocked_mv_f64 takes
 
     def trmv(self, P, name, x, alpha=1.0, beta=0.0, z=None, out=None):
-        """out = alpha * P.<name> x + beta * z   (name in LTi / LTit / LAi / LAit)."""
+        """out = alpha * P.<name> x + beta * z   (name in LTi / LTit / LAi / LAit).  A partial inverse of T (P.blocks) is
+        multiplied block by block, natively (odx_tri_blocked_mv_f64)."""
         if out is None:
             out = torch.empty(P.M, dtype=torch.float64, device=self.device)
+        if P.blocks and name in ("LTi", "LTit"):
+            bounds = self._bounds.get(P.blocks)
+            if bounds is None:
+                bounds = self._bounds[P.blocks] = (ctypes.c_int64 * len(P.blocks))(*P.blocks)
+            ws = self._workspace("tri_blocked_mv", self.lib.odx_tri_blocked_mv_workspace_bytes(P.M))
+            hip.check(self.lib.odx_tri_blocked_mv_f64(_p(getattr(P, name)), P.ld, P.M, self._TRI[name], bounds, len(P.blocks) - 1,
+                                                      _p(x), float(alpha), float(beta), _p(z), _p(out), _p(ws), ws.numel(),
+                                                      self._stream()), "odx_tri_blocked_mv_f64")
+            return out
         hip.check(self.lib.odx_trmv_f64(_p(getattr(P, name)), P.ld, P.M, self._TRI[name], _p(x), float(alpha),
                                         float(beta), _p(z), _p(out), self._stream()), "odx_trmv_f64")
         return out

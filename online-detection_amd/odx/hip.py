@@ -124,6 +124,9 @@ SIGNATURES = {
     "odx_falkon_precond_path_f64": (_i32, [_vp, _i64, _i64, _i32, _f64, _vp, _i32, _f64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "odx_falkon_precond_batched_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "odx_falkon_precond_batched_f64": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _f64, _f64, _f64, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "odx_falkon_precond_batched_partial_f64": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _f64, _f64, _f64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "odx_tri_blocked_mv_workspace_bytes": (_i64, [_i64]),
+    "odx_tri_blocked_mv_f64": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _f64, _f64, _vp, _vp, _vp, _i64, _vp]),
     "odx_trmv_f64": (_i32, [_vp, _i64, _i64, _i32, _vp, _f64, _f64, _vp, _vp, _vp]),
     "odx_trmvn_f64": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i64, _f64, _f64, _vp, _i64, _vp, _i64, _vp]),
     "odx_cg_init": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -136,6 +139,7 @@ SIGNATURES = {
     "odx_potrf_f64": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "odx_trtri_workspace_bytes": (_i64, [_i64]),
     "odx_trtri_f64": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "odx_trtri_partial_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
     "odx_convert_f32_f64": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _vp]),
     "odx_convert_f64_f32": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _vp]),
     "odx_rls_gram_workspace_bytes": (_i64, [_i64, _i32]),

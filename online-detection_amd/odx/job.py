@@ -62,6 +62,22 @@ class _Side:
         return ev
 
 
+def t_inverse_stop(M, unmerged, force=0):
+    """THE rule for who gets a partial inverse of T (backend.precond_batched's t_stop; 0 = fully merged).  Only a lock-step job
+    asks, only for more than 8192 centres, and only the top `unmerged` (1 or 2) merge levels of 4096 rows and more stay
+    unmerged: at M = 10 000, 1 -> 8192 (blocks 8192 | 1808), 2 -> 4096 (4096 | 4096 | 1808).  No problem of 8192 centres or
+    fewer changes.  force > 0 (the library's test hook "t_inverse_force_stop"): that level for every size with rows beyond it."""
+    M, unmerged, force = int(M), int(unmerged), int(force)
+    if force > 0:
+        return force if M > force else 0
+    if unmerged <= 0 or M <= 8192:
+        return 0
+    top = 128
+    while 2 * top < M:
+        top *= 2                          # the last merge level: the largest 128 2^k below M
+    return max(top >> (unmerged - 1), 4096)
+
+
 def _wait(ev):
     if ev is not None:
         torch.cuda.current_stream().wait_event(ev)
@@ -211,6 +227,20 @@ class LockstepClassJob:
                     with side:
                         be._workspace("precond_group", be.lib.odx_falkon_precond_batched_workspace_bytes(self.M, D, self.G))
 
+    def _t_stop(self):
+        """The stop level of T's inverse for this job's class-batched chains (t_inverse_stop, from the library's options)."""
+        lib = getattr(self.be, "lib", None)
+        if lib is None or not hasattr(lib, "odx_get_option"):
+            return 0
+        import ctypes
+        got = {}
+        for name in ("t_inverse_unmerged", "t_inverse_force_stop"):
+            v = ctypes.c_int(0)
+            if lib.odx_get_option(name.encode(), ctypes.byref(v)) != 0:
+                raise RuntimeError("odx_get_option(%s) failed" % name)
+            got[name] = v.value
+        return t_inverse_stop(self.M, got["t_inverse_unmerged"], got["t_inverse_force_stop"])
+
     def release(self):
         self.kbufs, self.pbuf, self.pgroup, self.scores, self.sbuf = [], [], [], None, None
 
@@ -339,7 +369,7 @@ class LockstepClassJob:
                         while len(self.pgroup) < self.lookahead + 1:
                             self.pgroup.append(torch.empty((self.G, 4, self.M, self.ld_p), dtype=torch.float64, device=dev))
                         plist = be.precond_batched(zf, self.sigma, self.lam, self.opt.pc_epsilon,
-                                                   out=self.pgroup[slot][:len(own)], ws_key="precond_group")
+                                                   out=self.pgroup[slot][:len(own)], ws_key="precond_group", t_stop=self._t_stop())
                     else:                 # a backend without the batched chain (tests' oracle backend): one after the other
                         plist = [be.precond(z, self.sigma, self.lam, self.opt.pc_epsilon) for z in zf]
                 ev = side.mark()
@@ -367,7 +397,7 @@ class LockstepClassJob:
                         while len(self.pgroup) < 2:
                             self.pgroup.append(torch.empty((g, 4, self.M, self.ld_p), dtype=torch.float64, device=dev))
                         plist = be.precond_batched(Zs, self.sigma, self.lam, self.opt.pc_epsilon,
-                                                   out=self.pgroup[gi % 2][:len(cls)], ws_key="precond_group")
+                                                   out=self.pgroup[gi % 2][:len(cls)], ws_key="precond_group", t_stop=self._t_stop())
                     else:
                         plist = [be.precond(z, self.sigma, self.lam, self.opt.pc_epsilon) for z in Zs]
                 ev = self.gside.mark()

@@ -338,6 +338,8 @@ class PathOps:
         """out[t] = alpha * P.<name> X[t] + beta * Z[t] over the rows of (T, >= P.M) f64 matrices: groups of up to 8 rows from
         ONE read of the factor each (odx_trmvn_f64); one row goes through trmv.  out may be Z, not X."""
         T, M = X.shape[0], P.M
+        from .backend import require_merged
+        require_merged(P, "trmvn")
         if out is None:
             out = torch.zeros((T, P.ld), dtype=torch.float64, device=self.device)
         for nm, t in (("X", X), ("out", out)) + (() if Z is None else (("Z", Z),)):

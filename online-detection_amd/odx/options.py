@@ -143,7 +143,9 @@ def override(**kw):
 
 
 def library_hook(name, value):
-    """The library's TEST HOOKS (include/odx.h: rls_force_nt_gram, rls_force_inverse_solve) — not options of the product."""
+    """The library's TEST HOOKS (include/odx.h: rls_force_nt_gram, rls_force_inverse_solve, t_inverse_force_stop) — not options of
+    the product — and its one option without a field here, t_inverse_unmerged (0 | 1 | 2 top merge levels of T's inverse that a
+    lock-step job above 8192 centres leaves unmerged: odx.job.t_inverse_stop; the table's fields are pinned by tests/test_abi.py)."""
     from . import hip
     hip.check(hip.load().odx_set_option(name.encode(), int(value)), "odx_set_option(%s)" % name)
 

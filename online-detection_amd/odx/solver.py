@@ -317,7 +317,8 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
         can_fold = allreduce is None and _can_fold(be, K, M, int(n))
 
     b0 = ar(b0)                                        # K' (y / n), summed over shards
-    one_call = shard is None and allreduce is None and phase is None and hasattr(be, "cg_solve") and not acc
+    one_call = (shard is None and allreduce is None and phase is None and hasattr(be, "cg_solve") and not acc
+                and not getattr(P, "blocks", ()))           # (the library loops read T's inverse whole: a partial one goes below)
     if one_call and getattr(K, "fmt", "f32") != "f32":
         # compact-format block: the class-batched library loop with a batch of one (odx_falkon_cg_batched_q_f64), where the
         # block's pass configuration has one and the factors are one contiguous block (and the block holds every column of

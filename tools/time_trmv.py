@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """The CG's triangular products alone (development aid): odx_trmv_f64 with a lower and an upper M x M factor, M = 1e4 (400 MB per
-product): microseconds per launch and TB/s, and the product against numpy at M = 700."""
+product): microseconds per launch and TB/s, and the product against numpy at M = 700.  Then the same bytes as a BLOCKED product
+(odx_tri_blocked_mv_f64, the form a partial inverse of T is multiplied in) with one and two levels unmerged: 3 and 5 launches."""
+import ctypes
 import os
 import sys
 import time
@@ -39,3 +41,23 @@ for M in (700, 10000):
             torch.cuda.synchronize()
             best = min(best, (time.perf_counter() - t0) / 200)
         print("M = %d %s: %.1f us per product, %.2f TB/s" % (M, name, best * 1e6, M * (M + 1) / 2 * 8 / best / 1e12))
+
+M = 10000
+ws = torch.empty(be.lib.odx_tri_blocked_mv_workspace_bytes(M), dtype=torch.uint8, device="cuda")
+for bounds in ((0, 8192, M), (0, 4096, 8192, M)):
+    arr = (ctypes.c_int64 * len(bounds))(*bounds)
+    for uplo, name in ((0, "lower"), (1, "upper")):
+        def run():
+            hip.check(be.lib.odx_tri_blocked_mv_f64(_p(A), ld, M, uplo, arr, len(bounds) - 1, _p(x), 1.0, 0.0, None, _p(y), _p(ws),
+                                                    ws.numel(), be._stream()), "odx_tri_blocked_mv_f64")
+        run()
+        torch.cuda.synchronize()
+        best = 1e9
+        for _ in range(5):
+            t0 = time.perf_counter()
+            for _ in range(200):
+                run()
+            torch.cuda.synchronize()
+            best = min(best, (time.perf_counter() - t0) / 200)
+        print("M = %d %s, blocks %s: %.1f us per product (%d launches), %.2f TB/s"
+              % (M, name, bounds, best * 1e6, 2 * len(bounds) - 3, M * (M + 1) / 2 * 8 / best / 1e12))
