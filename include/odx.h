@@ -183,6 +183,18 @@ int odx_gauss_mmvn_h2(const void* PX, int64_t ldpx, const float* metax, const fl
                       const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
                       double sigma, const double* V, int64_t ldv, int T,
                       float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* The same with a kernel width PER COLUMN (the members of a (sigma, lambda) grid over shared centres): sigmas is a HOST
+ * array of T widths, every one > 0 (ODX_ERR_INVALID otherwise).  The contraction X Z' does not depend on sigma, so a tile is
+ * still contracted once per group of up to 8 columns; each column then forms its entries with its own exponent (T times
+ * the exps of odx_gauss_mmvn_h2, nothing else).  Column c of out is bit for bit column c of odx_gauss_mmvn_h2 called with
+ * the same V, T, n, M and sigma = sigmas[c] (same tile core for T columns, same groups, same f64 sums); with all widths
+ * equal the whole output equals that call's.  The scaled exponents go to the kernels by value: one launch per group of up
+ * to 8 columns, no allocation, no copy.  Workspace bytes equal odx_gauss_mmvn_h2_workspace_bytes(n, M, T). */
+int64_t odx_gauss_mmvn_h2_sigmas_workspace_bytes(int64_t n, int64_t M, int T);
+int odx_gauss_mmvn_h2_sigmas(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                             const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                             const double* sigmas, const double* V, int64_t ldv, int T,
+                             float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 /* ---------------------------------------------------------------- A4: CG pass on stored K
  * falkon's incore_fdmmv on the stored K_nM (selected by store_kernel_d_threshold=250,
@@ -240,6 +252,24 @@ int odx_gauss_knm_h2_store(const void* PX, int64_t ldpx, const float* metax, con
                            const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
                            double sigma, int fmt, void* K, int64_t ldk, void* Klo, int64_t ldlo, const double* w,
                            double* ktw, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* The blocks of S kernel widths over the same rows and centres from ONE contraction of X Z' (a search over sigma): the main
+ * loop of the build runs once per tile and the epilogue once per width, against that width's block.  sigmas is a HOST array
+ * of S widths, K and Klo HOST arrays of S device pointers (Klo: ODX_KNM_U24 only) — as the lams of
+ * odx_falkon_precond_path_f64; the launch carries the scaled exponents and the pointers by value, the entry makes no
+ * allocation and no copy.  1 <= S <= ODX_GRID_MAX_SIGMAS, every sigma > 0, all three formats; all blocks share ldk (ldlo).
+ * w may be NULL; then ktw is not touched.  Bit for bit: block s, pad columns [M, ld) included, is what
+ * odx_gauss_knm_h2_store writes for sigmas[s] with the same other arguments, and row s of ktw (ldktw >= M doubles apart)
+ * is that call's ktw; equal widths give equal blocks.  Always on the 256 x 256 core.  Workspace (w given): S times
+ * odx_gauss_knm_h2_rhs_workspace_bytes(n, M).  ODX_ERR_INVALID: S outside the range, a sigma <= 0, a null block pointer;
+ * ODX_ERR_WORKSPACE: workspace too small; n <= 0: ODX_OK, nothing written. */
+#define ODX_GRID_MAX_SIGMAS 4
+int64_t odx_gauss_knm_h2_store_sigmas_workspace_bytes(int64_t n, int64_t M, int S);
+int odx_gauss_knm_h2_store_sigmas(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                                  const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                                  const double* sigmas, int S, int fmt,
+                                  void* const* K, int64_t ldk, void* const* Klo, int64_t ldlo,
+                                  const double* w, double* ktw, int64_t ldktw,
+                                  void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 int64_t odx_knm_fwd_bwd_q_workspace_bytes(int64_t n, int64_t M, int fmt);
 int odx_knm_fwd_bwd_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
                       const double* v, const double* w, double* out, void* workspace, int64_t workspace_bytes,

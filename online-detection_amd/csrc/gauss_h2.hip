@@ -1241,6 +1241,103 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_knm_h2w256_kernel(
   }
 }
 
+// ---- a grid of kernel widths from ONE contraction (odx_gauss_knm_h2_store_sigmas)
+// Nothing in the main loop depends on sigma: the accumulators hold x . z, and the width enters in the epilogue only.  This
+// sibling of gauss_knm_h2w256_kernel<RHS, FMT, CORE_H2> runs the main loop once and then knm_tile_epilogue once per width
+// against that width's block, planes and slab: S blocks for one contraction plus S epilogues.  Per width every constant is
+// formed by the single f32 operations of the kernel above (m2g = (-2 / (s_x s_z)) * g, xg = xsq * g, zg = zsq * g; no
+// contraction into a neighbouring add: fp contract is off in this body) and the epilogue is the same code: block s is bit
+// for bit what the kernel above stores for sigma_s.  The widths' scaled exponents and pointers come by value.
+struct KnmSigmaArgs {
+  float g2[ODX_GRID_MAX_SIGMAS];              // gamma log2(e) of each width
+  void* K[ODX_GRID_MAX_SIGMAS];
+  unsigned char* Klo[ODX_GRID_MAX_SIGMAS];
+  double* wslab[ODX_GRID_MAX_SIGMAS];
+};
+
+template <bool RHS, int FMT>
+__global__ __launch_bounds__(W_THREADS, 1) void gauss_knm_sigmas_h2w256_kernel(
+    const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
+    const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
+    int stages, int S, KnmSigmaArgs sg, int64_t ldk, int64_t ldlo, int gr, const double* __restrict__ w, int64_t wslab_ld) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int64_t GR = gr;
+  const int64_t tiles_n = (M + W_BN - 1) / W_BN;
+  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t band = wg / (GR * tiles_n), within = wg % (GR * tiles_n);
+  const int64_t i0 = (band * GR + within % GR) * W_BM, j0 = (within / GR) * W_BN;
+  if (i0 >= n) return;
+
+  __shared__ __attribute__((aligned(16))) float xg_s[ODX_GRID_MAX_SIGMAS][W_BM];      // row norms times each width's gamma log2(e)
+  __shared__ double ws_s[RHS ? W_BM : 1];
+  if (threadIdx.x < W_BM) {
+    const bool in = i0 + threadIdx.x < n;
+    const float xq = in ? xsq[i0 + threadIdx.x] : 0.f;
+#pragma unroll 1
+    for (int s = 0; s < S; ++s) xg_s[s][threadIdx.x] = in ? xq * sg.g2[s] : 0.f;
+    if (RHS) ws_s[threadIdx.x] = in ? w[i0 + threadIdx.x] : 0.0;   // rows past the end weigh nothing
+  }
+
+  f32x4 acc[8][4];
+  w_zero(acc);
+  w_mainloop_dma<true, CORE_H2>(acc, PX, ldpx, n, PZ, ldpz, M, i0, j0, stages, lds);      // its barriers also publish xg_s
+
+  const float m2 = -2.f / (metax[0] * metaz[0]);            // the scales are powers of two: exact
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wr = wave >> 2, wc = wave & 3;
+  const int cb = wc * 64 + 4 * (lane & 15);                 // first of this lane's four adjacent columns inside the tile
+  const int rl0 = wr * 128 + 4 * (lane >> 4);               // first of this lane's rows inside the tile
+  const int64_t mpad = FMT == KF_F32 ? ((M + 3) & ~int64_t(3)) : ((M + 7) & ~int64_t(7));
+  const bool interior = i0 + W_BM <= n && j0 + W_BN <= M;
+  const bool cols_in = j0 + cb < mpad;                      // groups of four: entirely inside the padded row or not at all
+  float zq[4];
+#pragma unroll
+  for (int tn = 0; tn < 4; ++tn) zq[tn] = j0 + cb + tn < M ? zsq[j0 + cb + tn] : 0.f;
+  const int64_t e0 = (i0 + rl0) * ldk + j0 + cb;            // this lane's first entry
+  const int esz = FMT == KF_F32 ? 4 : 2;
+  // the accumulators stay live across the S epilogues; the stage buffers are free (the main loop ended on a barrier) and
+  // take the S pairs of half-tile column sums in disjoint regions: one barrier for all of them
+#pragma unroll 1
+  for (int s = 0; s < S; ++s) {
+    const float g = sg.g2[s];
+    const float m2g = m2 * g;
+    float zg[4];
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) zg[tn] = j0 + cb + tn < M ? zq[tn] * g : -__builtin_inff();
+    double csum[4] = {0.0, 0.0, 0.0, 0.0};
+    // What the epilogue derives from the lane's place and the pitches (32 row offsets, 32 store predicates) does not depend
+    // on s, and hoisted out of this loop it would live beside the 128 accumulators: they went to scratch.  The values are
+    // made opaque per width (no instruction), so every epilogue derives them anew, as the one of the kernel above does.
+    int64_t shi = ldk * esz, slo = ldlo, rows_left = n - i0 - rl0;
+    int rl = rl0;
+    asm volatile("" : "+s"(shi), "+s"(slo), "+v"(rows_left), "+v"(rl));
+    char* phi = static_cast<char*>(sg.K[s]) + e0 * esz;
+    char* plo = FMT == KF_U24 ? reinterpret_cast<char*>(sg.Klo[s]) + (i0 + rl0) * ldlo + j0 + cb : nullptr;
+    knm_tile_epilogue<RHS, FMT>(acc, xg_s[s], ws_s, rl, m2g, zg, interior, cols_in, rows_left, phi, shi, plo, slo, csum);
+    if (RHS) {
+      double* red2 = reinterpret_cast<double*>(lds) + s * 2 * W_BN;
+#pragma unroll
+      for (int tn = 0; tn < 4; ++tn) {
+        double c = csum[tn];
+        c += __shfl_xor(c, 16);
+        c += __shfl_xor(c, 32);
+        if (lane < 16) red2[wr * W_BN + cb + tn] = FMT == KF_U24 ? c * 5.9604644775390625e-08 : c;   // 2^-24: exact
+      }
+    }
+  }
+  if (RHS) {
+    __syncthreads();
+    if (threadIdx.x < W_BN && j0 + threadIdx.x < M) {
+#pragma unroll 1
+      for (int s = 0; s < S; ++s) {
+        const double* red2 = reinterpret_cast<const double*>(lds) + s * 2 * W_BN;
+        sg.wslab[s][(i0 / W_BM) * wslab_ld + j0 + threadIdx.x] = red2[threadIdx.x] + red2[W_BN + threadIdx.x];
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- plain products on the split tile cores
 // out (m x n) = act(A B' + bias[col] + residual) for operands in the packed two-term f16 form (odx_split_f16): the f32
 // product at f32 accuracy on the f16 matrix cores, 3 MFMAs per product — ~3 x the rate of the f32 MFMA path for the
@@ -1988,6 +2085,230 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_h2w256_kernel(
   }
 }
 
+// ---- shared-centre scoring with a kernel width PER COLUMN (odx_gauss_mmvn_h2_sigmas): the members of a (sigma, lambda) grid
+// The two kernels above write a tile's entries over the accumulators once and weigh them NV times.  With a width per column
+// the accumulators keep instead what does not depend on sigma — the clamped d^2 in the wide kernel's form, the raw product
+// in the s16 kernel's, whose form pre-scales the norms by gamma — and every column forms its entries with its own exponent,
+// by the per-column kernels' own expressions (gauss_mmv_h2w256_kernel / gauss_mmv_h2s16_kernel): column c is bit for bit
+// the per-column launch with sigma_c.  The price is NV times the exps (128 / 64 v_exp_f32 per lane, column and tile).  One
+// launch serves one group of up to 8 columns, whose scaled exponents come by value (padding columns repeat the last one).
+struct MmvnGammas {
+  float g[8];
+};
+
+template <int NV, int CORE>
+__global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_sigmas_h2w256_kernel(
+    const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
+    const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
+    int stages, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
+    double* __restrict__ slab, int64_t slab_ld) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ __attribute__((aligned(16))) float xs_s[W_BM];
+  constexpr int PARK = NV < 3 ? NV : 3;                // (see gauss_mmvn_h2w256_kernel)
+  __shared__ double park[PARK][4][W_BM];
+  constexpr int64_t GR = 8;
+  const int c0 = cbase + (int)blockIdx.y * NV;
+  const int nc = T - c0 < NV ? T - c0 : NV;
+  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t band = wg / (GR * G), within = wg % (GR * G);
+  const int64_t i0 = (band * GR + within % GR) * W_BM;
+  const int g = (int)(within / GR);
+  const int64_t s0 = (int64_t)g * tg * W_BN;
+  const int64_t s1 = (s0 + (int64_t)tg * W_BN < M) ? s0 + (int64_t)tg * W_BN : M;
+  if (i0 >= n || s0 >= M) return;
+  const float m2 = -2.f / (metax[0] * metaz[0]);
+  double* red = reinterpret_cast<double*>(lds);       // [NV][4 (wc)][W_BM], over the operand images (w_mainloop_dma ends on a barrier)
+
+  if (threadIdx.x < W_BM) xs_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] : 0.f;
+  double tot[NV - PARK + 1][2];           // (+ 1: no empty array at NV = 2)
+#pragma unroll
+  for (int c = 0; c < NV - PARK; ++c) tot[c][0] = tot[c][1] = 0.0;
+  {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* mine = &park[0][wave & 3][(wave >> 2) * 128 + 16 * ((lane & 15) >> 2) + 4 * (lane >> 4) + (lane & 3)];
+#pragma unroll
+    for (int c = 0; c < PARK; ++c) mine[c * 4 * W_BM] = mine[c * 4 * W_BM + 64] = 0.0;
+  }
+
+  for (int64_t j0 = s0; j0 < s1; j0 += W_BN) {
+    f32x4 acc[8][4];
+    w_zero(acc);
+    w_mainloop_dma<false, CORE>(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, stages, lds);
+    int tid = threadIdx.x;                              // (derived here, opaquely: see gauss_mmvn_h2w256_kernel)
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wr = tid >> 8, wc = (tid >> 6) & 3;
+    const bool b8 = lane & 8, b4 = lane & 4, b2 = lane & 2, b1 = lane & 1;
+    const int slot = wc * W_BM + wr * 128 + 16 * ((lane & 15) >> 2) + 4 * (lane >> 4) + (lane & 3);
+    double* mine = red + slot;
+    double* parked = &park[0][0][0] + slot;
+#pragma unroll
+    for (int c = 0; c < NV - PARK; ++c) mine[c * 4 * W_BM] = tot[c][0], mine[c * 4 * W_BM + 64] = tot[c][1];
+    float zs[4];
+    const int64_t col0 = j0 + wc * 64 + (lane & 15);       // this lane's columns: col0 + 16 tn; past the group / M: weight 0
+    const double* vp = V + col0 * ldv + c0;
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) zs[tn] = col0 + 16 * tn < s1 ? zsq[col0 + 16 * tn] : 0.f;
+    // the accumulators become the clamped squared distances: the part of an entry every width shares
+#pragma unroll
+    for (int tm = 0; tm < 8; ++tm)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float xs = xs_s[wr * 128 + tm * 16 + 4 * (lane >> 4) + q];
+#pragma unroll
+        for (int tn = 0; tn < 4; ++tn) {
+          const float d2 = fmaf(m2, acc[tm][tn][q], xs) + zs[tn];
+          acc[tm][tn][q] = fmaxf(d2, 0.f);
+        }
+      }
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      mmvn_fresh(acc);
+      const float gc = gm.g[c];
+      double al[4];
+#pragma unroll
+      for (int tn = 0; tn < 4; ++tn) al[tn] = (col0 + 16 * tn < s1 && c < nc) ? vp[16 * tn * ldv + c] : 0.0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        double w8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {       // slots j (tm' = j >> 2) and j + 8 (tm' = 2 + (j >> 2)), q = j & 3
+          double v[2];
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            const int tm = 4 * h + 2 * u + (j >> 2), q = j & 3;
+            v[u] = 0.0;
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn) v[u] = fma((double)__builtin_amdgcn_exp2f(acc[tm][tn][q] * gc), al[tn], v[u]);
+          }
+          w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+        }
+        double w4[4], w2[2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
+        double* sum = c < PARK ? parked + c * 4 * W_BM + 64 * h : mine + (c - PARK) * 4 * W_BM + 64 * h;
+        *sum += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+      }
+    }
+    if (j0 + W_BN < s1) {
+#pragma unroll
+      for (int c = 0; c < NV - PARK; ++c) tot[c][0] = mine[c * 4 * W_BM], tot[c][1] = mine[c * 4 * W_BM + 64];
+    }
+    __syncthreads();                  // the next main loop writes the images at once; behind the last tile: `red` is complete
+  }
+  if (threadIdx.x < W_BM) {
+    const int64_t row = i0 + threadIdx.x;
+    if (row < n)
+      for (int c = 0; c < nc; ++c) {
+        const double* rc = (c < PARK ? &park[0][0][0] + c * 4 * W_BM : red + (c - PARK) * 4 * W_BM) + threadIdx.x;
+        slab[((int64_t)(c0 + c) * G + g) * slab_ld + row] = (rc[0] + rc[W_BM]) + (rc[2 * W_BM] + rc[3 * W_BM]);
+      }
+  }
+}
+
+template <int NV>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_sigmas_h2s16_kernel(
+    const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
+    const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
+    int ktiles, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
+    double* __restrict__ slab, int64_t slab_ld) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ __attribute__((aligned(16))) float xg_s[NV][GEMM_BM];      // row norms times each column's gamma log2(e)
+  constexpr int64_t GR = 8;
+  const int c0 = cbase + (int)blockIdx.y * NV;
+  const int nc = T - c0 < NV ? T - c0 : NV;
+  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t band = wg / (GR * G), within = wg % (GR * G);
+  const int64_t i0 = (band * GR + within % GR) * GEMM_BM;
+  const int g = (int)(within / GR);
+  const int64_t s0 = (int64_t)g * tg * GEMM_BN;
+  const int64_t s1 = (s0 + (int64_t)tg * GEMM_BN < M) ? s0 + (int64_t)tg * GEMM_BN : M;
+  if (i0 >= n || s0 >= M) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const float m2 = -2.f / (metax[0] * metaz[0]);
+
+  if (threadIdx.x < GEMM_BM) {
+    const bool in = i0 + threadIdx.x < n;
+    const float xq = in ? xsq[i0 + threadIdx.x] : 0.f;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) xg_s[c][threadIdx.x] = in ? xq * gm.g[c] : 0.f;
+  }
+  double tot[NV];
+#pragma unroll
+  for (int c = 0; c < NV; ++c) tot[c] = 0.0;
+  const bool b8 = lane & 8, b4 = lane & 4, b2 = lane & 2, b1 = lane & 1;
+
+  for (int64_t j0 = s0; j0 < s1; j0 += GEMM_BN) {
+    f32x4 acc[4][4];
+    s16_zero(acc);
+    s16_mainloop(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, ktiles, lds);     // its barriers also publish xg_s
+    float zq[4];
+    int64_t voff[4];                    // < 0: a column past the group / M (weight 0)
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) {
+      const int64_t col = j0 + wc * 64 + tn * 16 + (lane & 15);
+      const bool cv = col < s1;
+      zq[tn] = cv ? zsq[col] : 0.f;
+      voff[tn] = cv ? col * ldv + c0 : -1;
+    }
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      mmvn_fresh(acc);
+      const float gc = gm.g[c];
+      const float m2g = m2 * gc;
+      float zs[4];
+      double al[4];
+#pragma unroll
+      for (int tn = 0; tn < 4; ++tn) {
+        zs[tn] = voff[tn] >= 0 ? zq[tn] * gc : 0.f;
+        al[tn] = (voff[tn] >= 0 && c < nc) ? V[voff[tn] + c] : 0.0;
+      }
+      double w8[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {       // slots j (tm = j >> 2) and j + 8 (tm = 2 + (j >> 2)), q = j & 3
+        double v[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int tm = 2 * u + (j >> 2), q = j & 3;
+          const float xs = xg_s[c][wr * 64 + tm * 16 + 4 * (lane >> 4) + q];
+          v[u] = 0.0;
+#pragma unroll
+          for (int tn = 0; tn < 4; ++tn) {
+            const float e = fminf(fmaf(m2g, acc[tm][tn][q], xs) + zs[tn], 0.f);     // gamma < 0: d^2 >= 0 <=> e <= 0
+            v[u] = fma((double)__builtin_amdgcn_exp2f(e), al[tn], v[u]);
+          }
+        }
+        w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+      }
+      double w4[4], w2[2];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
+      tot[c] += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+    }
+  }
+  __syncthreads();                            // every wave is done with the operand images: `red` takes their place
+  double* red = reinterpret_cast<double*>(lds);       // [NV][2 (wr)][2 (wc)][64]
+  {
+    const int slot = lane & 15;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) red[((c * 2 + wr) * 2 + wc) * 64 + (slot >> 2) * 16 + 4 * (lane >> 4) + (slot & 3)] = tot[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int w = threadIdx.x >> 6, rr = threadIdx.x & 63;
+    const int64_t row = i0 + w * 64 + rr;
+    if (row < n)
+      for (int c = 0; c < nc; ++c)
+        slab[((int64_t)(c0 + c) * G + g) * slab_ld + row] = red[((c * 2 + w) * 2 + 0) * 64 + rr] + red[((c * 2 + w) * 2 + 1) * 64 + rr];
+  }
+}
+
 constexpr int MMV_TG = 4;   // column tiles per workgroup (2 / 4 / 8 / 16 / 40 measured: 342 / 341 / 335 / 321 / 305 TF)
 
 constexpr int W_MMV_TG = 2; // column tiles per workgroup on the 256 x 256 core (1 / 2 / 4 / 8 measured: 409 / 419 / 412 / 395 TF)
@@ -2722,6 +3043,88 @@ extern "C" int odx_gauss_knm_h2_store(const void* PX, int64_t ldpx, const float*
                         Klo, ldlo, w, ktw, workspace, workspace_bytes, stream);
 }
 
+// ---- S blocks, one per kernel width, from one contraction (gauss_knm_sigmas_h2w256_kernel)
+extern "C" int64_t odx_gauss_knm_h2_store_sigmas_workspace_bytes(int64_t n, int64_t M, int S) {
+  if (S <= 0) return 0;
+  return (int64_t)S * odx_gauss_knm_h2_rhs_workspace_bytes(n, M);
+}
+
+template <bool RHS, int FMT>
+static int launch_knm_sigmas_t(unsigned wt, hipStream_t s, const uint32_t* PX, int64_t ldpx, const float* metax, const float* xsq,
+                               int64_t n, const uint32_t* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M,
+                               int stages, int S, const KnmSigmaArgs& sg, int64_t ldk, int64_t ldlo, int wgr, const double* w,
+                               int64_t wslab_ld) {
+  ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_knm_sigmas_h2w256_kernel<RHS, FMT>), W_LDS_BYTES));
+  hipLaunchKernelGGL((gauss_knm_sigmas_h2w256_kernel<RHS, FMT>), dim3(wt), dim3(W_THREADS), W_LDS_BYTES, s, PX, ldpx, metax, xsq, n,
+                     PZ, ldpz, metaz, zsq, M, stages, S, sg, ldk, ldlo, wgr, w, wslab_ld);
+  return ODX_OK;
+}
+
+extern "C" int odx_gauss_knm_h2_store_sigmas(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                                             const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                                             const double* sigmas, int S, int fmt, void* const* K, int64_t ldk, void* const* Klo,
+                                             int64_t ldlo, const double* w, double* ktw, int64_t ldktw, void* workspace,
+                                             int64_t workspace_bytes, odx_stream_t stream) {
+  const char* who = "odx_gauss_knm_h2_store_sigmas";
+  ODX_REQUIRE(M > 0, "%s: M <= 0", who);
+  ODX_REQUIRE(S >= 1 && S <= ODX_GRID_MAX_SIGMAS, "%s: S = %d outside 1 .. %d", who, S, ODX_GRID_MAX_SIGMAS);
+  ODX_REQUIRE(fmt == ODX_KNM_F32 || fmt == ODX_KNM_U24 || fmt == ODX_KNM_BF16, "%s: unknown storage format %d", who, fmt);
+  ODX_REQUIRE(sigmas && K && (fmt != ODX_KNM_U24 || Klo), "%s: null list of widths or blocks", who);
+  for (int s = 0; s < S; ++s) ODX_REQUIRE(sigmas[s] > 0, "%s: sigma[%d] <= 0", who, s);
+  if (n <= 0) return ODX_OK;
+  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && D > 0, "%s: bad argument", who);
+  ODX_REQUIRE(w == nullptr || (ktw != nullptr && ldktw >= M), "%s: w needs ktw with ldktw >= M", who);
+  const int64_t dp = round_up(D, H2_KT);
+  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
+              "%s: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)", who);
+  const int64_t ldmin = odx_knm_ld(M, fmt);
+  ODX_REQUIRE(ldk >= ldmin && ldk % (fmt == ODX_KNM_F32 ? 4 : 8) == 0, "%s: ldk must be a multiple of %d and >= %lld", who,
+              fmt == ODX_KNM_F32 ? 4 : 8, (long long)ldmin);
+  if (fmt == ODX_KNM_U24) ODX_REQUIRE(ldlo >= ldmin && ldlo % 8 == 0, "%s: ldlo %% 8 == 0 and ldlo >= roundup(M, 8) needed", who);
+  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24) && ldk < (1 << 24), "%s: leading dimensions must stay below 2^24 (32-bit tile offsets)", who);
+  KnmSigmaArgs sg;
+  for (int s = 0; s < ODX_GRID_MAX_SIGMAS; ++s) sg.g2[s] = 0.f, sg.K[s] = nullptr, sg.Klo[s] = nullptr, sg.wslab[s] = nullptr;
+  for (int s = 0; s < S; ++s) {
+    ODX_REQUIRE(K[s] && aligned16(K[s]), "%s: block %d is null or not 16-byte aligned", who, s);
+    if (fmt == ODX_KNM_U24) ODX_REQUIRE(Klo[s] && aligned16(Klo[s]), "%s: low-byte plane %d is null or not 16-byte aligned", who, s);
+    sg.g2[s] = (float)(-0.5 / (sigmas[s] * sigmas[s])) * LOG2E;
+    sg.K[s] = K[s];
+    sg.Klo[s] = fmt == ODX_KNM_U24 ? static_cast<unsigned char*>(Klo[s]) : nullptr;
+  }
+  const int64_t per = odx_gauss_knm_h2_rhs_workspace_bytes(n, M);
+  if (w != nullptr && (workspace == nullptr || !aligned16(workspace) || workspace_bytes < (int64_t)S * per)) {
+    set_error("%s: workspace too small", who);
+    return ODX_ERR_WORKSPACE;
+  }
+  const int64_t wld = round_up(M, 4);
+  if (w != nullptr)
+    for (int s = 0; s < S; ++s) sg.wslab[s] = reinterpret_cast<double*>(static_cast<char*>(workspace) + s * per);
+  // the grid and the band height of launch_knm_w256: the same tile order
+  const int wgr = 4;
+  const int64_t wt = round_up(ceil_div(n, W_BM), wgr) * ceil_div(M, W_BN);
+  ODX_REQUIRE(wt < (1ll << 31), "%s: grid too large", who);
+  hipStream_t hs = as_stream(stream);
+  const uint32_t *px = (const uint32_t*)PX, *pz = (const uint32_t*)PZ;
+  const int stages = (int)(dp / W_KS);
+#define ODX_KNM_SIG(RHS_, FMT_) \
+  ODX_PROPAGATE((launch_knm_sigmas_t<RHS_, FMT_>((unsigned)wt, hs, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages, S, sg, ldk, ldlo, wgr, w, wld)))
+#define ODX_KNM_SIG_F(RHS_)                          \
+  do {                                               \
+    if (fmt == ODX_KNM_F32) ODX_KNM_SIG(RHS_, KF_F32);      \
+    else if (fmt == ODX_KNM_U24) ODX_KNM_SIG(RHS_, KF_U24); \
+    else ODX_KNM_SIG(RHS_, KF_BF16);                        \
+  } while (0)
+  if (w != nullptr) ODX_KNM_SIG_F(true);
+  else ODX_KNM_SIG_F(false);
+#undef ODX_KNM_SIG_F
+#undef ODX_KNM_SIG
+  ODX_CHECK_LAUNCH("odx_gauss_knm_h2_store_sigmas");
+  if (w == nullptr) return ODX_OK;
+  for (int s = 0; s < S; ++s)
+    ODX_PROPAGATE(slab_reduce_f64(sg.wslab[s], wld, (int)ceil_div(n, W_BM), M, ktw + s * ldktw, hs));
+  return ODX_OK;
+}
+
 // ---------------------------------------------------------------- fp8 (OCP e4m3) contraction: BASELINE config 5's path
 // x . z with both operands rounded once to e4m3 (4 significant bits): K entries off by ~1e-3, scores by ~5e-3
 // (tools/precision_scoring_study.py) — a THROUGHPUT-ONLY variant, never the default; the fit's 1e-4 bar on alpha needs the
@@ -2975,6 +3378,85 @@ extern "C" int odx_gauss_mmvn_h2(const void* PX, int64_t ldpx, const float* meta
   hipLaunchKernelGGL(mmvn_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)T), dim3(256), 0, a.stream, a.slab, a.slab_ld,
                      a.G, n, out, ldo);
   ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2(reduce)");
+  return ODX_OK;
+}
+
+// ---- the same with a kernel width per column: one launch per group of up to 8 columns, its scaled exponents by value
+template <int NV, bool WIDE>
+static int launch_mmvn_sigmas_group(const MmvnArgs& a, const MmvnGammas& gm, int cbase) {
+  if (WIDE) {
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_sigmas_h2w256_kernel<NV, CORE_H2>), W_LDS_BYTES));
+    hipLaunchKernelGGL((gauss_mmvn_sigmas_h2w256_kernel<NV, CORE_H2>), dim3(a.wgs, 1u), dim3(W_THREADS), W_LDS_BYTES, a.stream,
+                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T, a.tg,
+                       a.G, a.slab, a.slab_ld);
+  } else {
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_sigmas_h2s16_kernel<NV>)));
+    hipLaunchKernelGGL((gauss_mmvn_sigmas_h2s16_kernel<NV>), dim3(a.wgs, 1u), dim3(GEMM_THREADS), S16_LDS_BYTES, a.stream,
+                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T, a.tg,
+                       a.G, a.slab, a.slab_ld);
+  }
+  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2_sigmas");
+  return ODX_OK;
+}
+
+template <bool WIDE>
+static int launch_mmvn_sigmas(const MmvnArgs& a, const double* sigmas) {
+  for (int cbase = 0; cbase < a.T; cbase += 8) {
+    const int rest = a.T - cbase < 8 ? a.T - cbase : 8;
+    MmvnGammas gm;
+    for (int c = 0; c < 8; ++c) {
+      const double sg = sigmas[cbase + (c < rest ? c : rest - 1)];
+      gm.g[c] = (float)(-0.5 / (sg * sg)) * LOG2E;
+    }
+    if (rest > 4) ODX_PROPAGATE((launch_mmvn_sigmas_group<8, WIDE>(a, gm, cbase)));
+    else if (rest > 2) ODX_PROPAGATE((launch_mmvn_sigmas_group<4, WIDE>(a, gm, cbase)));
+    else ODX_PROPAGATE((launch_mmvn_sigmas_group<2, WIDE>(a, gm, cbase)));
+  }
+  return ODX_OK;
+}
+
+extern "C" int64_t odx_gauss_mmvn_h2_sigmas_workspace_bytes(int64_t n, int64_t M, int T) {
+  return odx_gauss_mmv_h2_workspace_bytes(n, M, T);
+}
+
+extern "C" int odx_gauss_mmvn_h2_sigmas(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                                        const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                                        const double* sigmas, const double* V, int64_t ldv, int T, float* out, int64_t ldo,
+                                        void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  if (n <= 0 || T <= 0) return ODX_OK;
+  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && out && sigmas && D > 0 && ldv >= T && M > 0,
+              "odx_gauss_mmvn_h2_sigmas: bad argument");
+  for (int c = 0; c < T; ++c) ODX_REQUIRE(sigmas[c] > 0, "odx_gauss_mmvn_h2_sigmas: sigma[%d] <= 0", c);
+  const int64_t dp = round_up(D, H2_KT);
+  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
+              "odx_gauss_mmvn_h2_sigmas: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)");
+  ODX_REQUIRE(ldo >= T && T < 65536, "odx_gauss_mmvn_h2_sigmas: ldo < T or too many columns");
+  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24), "odx_gauss_mmvn_h2_sigmas: leading dimensions must stay below 2^24 (32-bit tile offsets)");
+  if (workspace == nullptr || workspace_bytes < odx_gauss_mmvn_h2_sigmas_workspace_bytes(n, M, T)) {
+    set_error("odx_gauss_mmvn_h2_sigmas: workspace too small");
+    return ODX_ERR_WORKSPACE;
+  }
+  MmvnArgs a;
+  a.PX = (const uint32_t*)PX, a.PZ = (const uint32_t*)PZ, a.ldpx = ldpx, a.ldpz = ldpz, a.n = n, a.M = M, a.ldv = ldv;
+  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T;
+  a.slab = static_cast<double*>(workspace), a.slab_ld = round_up(n, 2);
+  a.gamma_log2e = 0.f, a.stream = as_stream(stream);
+  // the tile core, the groups of column tiles and the slab of odx_gauss_mmvn_h2 for T columns: the same bits per column
+  const bool wide = h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
+  int64_t wgs;
+  if (wide) {
+    a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = (int)(dp / W_KS);
+    wgs = round_up(ceil_div(n, W_BM), 8) * a.G;
+  } else {
+    a.tg = mmv_tg(n, M, T), a.G = (int)mmv_groups(M, a.tg), a.kt = (int)(dp / H2_KT);
+    wgs = round_up(ceil_div(n, GEMM_BM), 8) * a.G;
+  }
+  ODX_REQUIRE(wgs < (1ll << 31), "odx_gauss_mmvn_h2_sigmas: grid too large");
+  a.wgs = (unsigned)wgs;
+  ODX_PROPAGATE(wide ? launch_mmvn_sigmas<true>(a, sigmas) : launch_mmvn_sigmas<false>(a, sigmas));
+  hipLaunchKernelGGL(mmvn_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)T), dim3(256), 0, a.stream, a.slab, a.slab_ld,
+                     a.G, n, out, ldo);
+  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2_sigmas(reduce)");
   return ODX_OK;
 }
 

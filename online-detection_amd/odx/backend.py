@@ -126,6 +126,11 @@ class HipBackend(PathOps):
     # wide_pass_min, not an option; None = never.  2: the route won at every measured shape from two columns on
     # (profiles/mmv_shared.md).
     shared_mmv_min = 2
+    # The fewest features (F.D) from which knm_rhs_sigmas builds the blocks of a group of kernel widths from ONE contraction
+    # (odx_gauss_knm_h2_store_sigmas); None = never (knm_rhs per width).  An attribute like wide_pass_min.  A build is bound by
+    # its stores, not its contraction, while D is small, and there the shared contraction saves nothing: measured slower
+    # than the single builds at D = 256 and 0.65 of their time at D = 1024, four widths (profiles/sigma_grid.md).
+    sigma_grid_min_features = 1024
 
     def __init__(self, device=None):
         self.lib = hip.require_gpu()
@@ -573,6 +578,63 @@ class HipBackend(PathOps):
             return K, self.ktk(K, w=w, out=rhs_out)
         return self._knm_store(F, Zf, sigma, "f32", w, out, rhs_out)
 
+    def _one_store_call(self, F, Zf):
+        """Whether knm_rhs at this shape is a single _knm_store call on the split-f16 core: what one call of
+        odx_gauss_knm_h2_store_sigmas can stand for, width after width."""
+        n, M = F.n, Zf.n
+        if self.gauss != "h2" or n <= 0 or getattr(Zf, "cmap", None) is not None:
+            return False
+        fmt = self.knm_format(n, M)
+        if fmt in ("u24", "bf16"):
+            return True
+        return fmt == "f32" and self.lib.odx_gauss_h2_tile(n, M) == 256 and not self.direct_small(n, M, F.D)
+
+    def knm_rhs_sigmas(self, F, Zf, sigmas, w, outs=None):
+        """[(K_s, K_s' w)] for the kernel widths `sigmas` over the same rows and centres: entry s is what
+        knm_rhs(F, Zf, sigmas[s], w) returns, bit for bit.  Where that is a single build on the split-f16 wide tile core
+        (_one_store_call) over at least sigma_grid_min_features features, the blocks of up to ODX_GRID_MAX_SIGMAS widths
+        come from ONE contraction of X Z' (odx_gauss_knm_h2_store_sigmas; a group of one width is that single build
+        itself); in every other situation (streamed shards, column-mapped centres, small or direct blocks, the f32 / f8
+        cores, few features) knm_rhs is looped.  outs: one preallocated buffer (or None) per width.  All blocks of a call
+        are resident together."""
+        sigmas = [float(s) for s in sigmas]
+        outs = [None] * len(sigmas) if outs is None else list(outs)
+        if len(outs) != len(sigmas):
+            raise ValueError("knm_rhs_sigmas: %d buffers for %d widths" % (len(outs), len(sigmas)))
+        least = self.sigma_grid_min_features
+        if least is None or F.D < least or not self._one_store_call(F, Zf):
+            return [self.knm_rhs(F, Zf, s, w, out=o) for s, o in zip(sigmas, outs)]
+        fmt = self.knm_format(F.n, Zf.n)
+        res = []
+        for g0 in range(0, len(sigmas), hip.GRID_MAX_SIGMAS):
+            grp = sigmas[g0:g0 + hip.GRID_MAX_SIGMAS]
+            if len(grp) == 1:
+                res.append(self._knm_store(F, Zf, grp[0], fmt, w, outs[g0], None))
+            else:
+                res += self._knm_store_sigmas(F, Zf, grp, fmt, w, outs[g0:g0 + len(grp)])
+        return res
+
+    def _knm_store_sigmas(self, F, Zf, sigmas, fmt, w, outs):
+        """The blocks of 1 .. ODX_GRID_MAX_SIGMAS widths in storage format `fmt` from one contraction on the wide tile core
+        (odx_gauss_knm_h2_store_sigmas), with the fused right-hand sides when w is given: [(K_s, K_s' w)]."""
+        n, M, S = F.n, Zf.n, len(sigmas)
+        self.pack(F), self.pack(Zf)
+        if w is not None:
+            w = w.to(dtype=torch.float64, device=self.device).contiguous()
+        Ks = [self._knm_block(n, M, fmt, outs[s]) for s in range(S)]
+        B = torch.empty((S, M), dtype=torch.float64, device=self.device)
+        ws = None
+        if w is not None:
+            ws = self._workspace("knm_rhs_sigmas", self.lib.odx_gauss_knm_h2_store_sigmas_workspace_bytes(n, M, S))
+        sig = (ctypes.c_double * S)(*[float(s) for s in sigmas])
+        hi = (ctypes.c_void_p * S)(*[K.K.data_ptr() for K in Ks])
+        lo = (ctypes.c_void_p * S)(*[K.lo.data_ptr() for K in Ks]) if fmt == "u24" else None
+        hip.check(self.lib.odx_gauss_knm_h2_store_sigmas(
+            _p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), n, _p(Zf.P), Zf.P.stride(0), _p(Zf.meta), _p(Zf.sq), M, F.D,
+            sig, S, hip.KNM_CODE[fmt], hi, Ks[0].ld, lo, Ks[0].ld, _p(w), _p(B if w is not None else None), M, _p(ws),
+            ws.numel() if ws is not None else 0, self._stream()), "odx_gauss_knm_h2_store_sigmas")
+        return [(Ks[s], B[s]) for s in range(S)]
+
     def pin_gauss_tile(self, tile):
         """Pin the tile core of the f16-split Gaussian kernels (128 or 256); 0 = chosen per launch (default)."""
         from . import options as _options
@@ -764,6 +826,45 @@ class HipBackend(PathOps):
             hip.check(self.lib.odx_gauss_mmv_f32(_p(F.X), F.ld, _p(F.sq), F.n, _p(Zf.X), Zf.ld, _p(Zf.sq), F.D,
                                                  float(sigma), _p(V), V.stride(0), _p(ranges), T, _p(out), out.stride(0),
                                                  self._stream()), "odx_gauss_mmv_f32")
+        return out
+
+    def mmv_sigmas(self, F, Zf, sigmas, V, out=None):
+        """(n, T) f32: column c = K_{sigmas[c]}(F, Zf) @ V[:, c] for a DENSE V (Mtot, T) f64 — the members of a (sigma, lambda)
+        grid over shared centres.  With gauss "h2" one contraction of X Z' per group of up to 8 columns serves every width
+        (odx_gauss_mmvn_h2_sigmas, on the tile core the dispatch rule picks for T columns): column c is bit for bit column c
+        of mmv(F, Zf, sigmas[c], V) on the shared route.  Otherwise mmv is looped over the distinct widths and their columns
+        copied."""
+        V = V.to(device=self.device, dtype=torch.float64)
+        if V.dim() == 1:
+            V = V[:, None]
+        Mtot, T = V.shape
+        sigmas = [float(s) for s in sigmas]
+        if len(sigmas) != T:
+            raise ValueError("mmv_sigmas: %d widths for %d columns" % (len(sigmas), T))
+        if any(not s > 0.0 for s in sigmas):
+            raise ValueError("mmv_sigmas: every sigma must be positive, got %r" % (sigmas,))
+        if Mtot != Zf.n:
+            raise ValueError("mmv_sigmas: V has %d rows but there are %d centres" % (Mtot, Zf.n))
+        if out is None:
+            out = torch.empty((F.n, T), dtype=torch.float32, device=self.device)
+        if F.n == 0 or T == 0:
+            return out
+        if Mtot == 0:
+            return out.zero_()
+        if self.gauss == "h2":
+            self.pack(F), self.pack(Zf)
+            if not (V.stride(1) == 1 and V.stride(0) >= T):
+                V = V.contiguous()
+            ws = self._workspace("mmv", self.lib.odx_gauss_mmvn_h2_sigmas_workspace_bytes(F.n, Mtot, T))
+            sig = (ctypes.c_double * T)(*sigmas)
+            hip.check(self.lib.odx_gauss_mmvn_h2_sigmas(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), F.n, _p(Zf.P), Zf.P.stride(0),
+                                                        _p(Zf.meta), _p(Zf.sq), Mtot, F.D, sig, _p(V), V.stride(0), T, _p(out),
+                                                        out.stride(0), _p(ws), ws.numel(), self._stream()),
+                      "odx_gauss_mmvn_h2_sigmas")
+            return out
+        for s in sorted(set(sigmas)):
+            cols = [c for c in range(T) if sigmas[c] == s]
+            out[:, cols] = self.mmv(F, Zf, s, V[:, cols].contiguous())
         return out
 
     # ------------------------------------------------------------------ RLS (A7)

@@ -20,7 +20,7 @@ import torch
 
 from . import backend as _backend
 from . import options as _options
-from .solver import SolverOptions, falkon_fit, falkon_fit_multi, falkon_fit_path
+from .solver import SolverOptions, falkon_fit, falkon_fit_grid, falkon_fit_multi, falkon_fit_path
 
 
 class FalkonOptions:
@@ -184,6 +184,47 @@ class _FalkonBase:
             out.append(est)
         return out
 
+    def fit_grid(self, X, Y, sigmas, penalties):
+        """One fitted estimator of this class per (sigma, penalty): S lists of L estimators, from one contraction of X Z' per
+        group of widths where the backend has one (solver.falkon_fit_grid).  The centres are selected once, as in fit_path,
+        and shared by all members (`ny_points_`); each member has its own GaussianKernel(sigma), `penalty` and `alpha_`.
+        This estimator is the template and stays as it is."""
+        import copy
+        be = _backend.get_backend()
+        F = be.features(X)
+        if isinstance(self.center_selection, str):
+            Zf = be.rows(F, torch.randperm(F.n)[: self.M])
+        else:
+            sel = self.center_selection.select(F.X, None)
+            Zf = be.features(sel[0] if isinstance(sel, tuple) else sel)
+        y = torch.as_tensor(Y).reshape(F.n, -1)
+        if y.shape[1] != 1:
+            raise ValueError("odx FALKON fits one right-hand side per model (the reference trains one "
+                             "binary classifier per fit); got Y with %d columns" % y.shape[1])
+        sigmas, penalties = [float(s) for s in sigmas], [float(p) for p in penalties]
+        alphas = falkon_fit_grid(be, F, be.vec(y[:, 0]), Zf, sigmas, penalties, int(self.maxiter), self.options.solver_options())
+        if hasattr(be, "release_helper_streams"):
+            be.release_helper_streams()
+        ny = Zf.X.contiguous() if Zf.X.stride(0) != Zf.D else Zf.X
+        if self._cpu_model:
+            ny = ny.cpu()                    # once: the members share ONE tensor (predict_grid asks for that)
+        out = []
+        for s, sigma in enumerate(sigmas):
+            row = []
+            for l, pen in enumerate(penalties):
+                est = copy.copy(self)
+                est.__dict__.pop("_zf", None)
+                est.kernel = GaussianKernel(sigma)
+                est.penalty, est.M = pen, Zf.n
+                est.alpha_, est.ny_points_ = alphas[s, l].clone().reshape(-1, 1), ny
+                if est._cpu_model:
+                    est.alpha_ = est.alpha_.cpu()
+                else:
+                    est._centres(Zf)
+                row.append(est)
+            out.append(row)
+        return out
+
     def _centres(self, Zf=None):
         """The centres as kernel operands (row norms, packed f16 split), kept with the model while `ny_points_` is the
         same, unmodified tensor: a predict is ~100 us of GPU work and re-deriving them was a third of its launches.
@@ -252,6 +293,37 @@ def predict_path(estimators, X):
             raise ValueError("predict_path: every alpha_ must be (M, 1), got %s" % (tuple(est.alpha_.shape),))
     V = torch.cat([est.alpha_ for est in estimators], dim=1)
     res = first.kernel.mmv(X, first._centres(), V, dense=True)
+    if first._cpu_model and not (torch.is_tensor(X) and X.is_cuda):
+        res = res.cpu()
+    return res
+
+
+def predict_grid(estimators, X):
+    """(n, T) f32: column t is ``estimators[t].predict(X)[:, 0]`` for fitted one-output estimators that share their centres
+    (one ``ny_points_`` tensor) and have ANY kernel widths — the members of a ``fit_grid``, flattened in any order — from
+    ONE dense scoring call over the stacked alphas (backend ``mmv_sigmas``: one contraction of X Z' per group of up to 8
+    columns on HipBackend, every column with its own exponent; bit for bit each distinct sigma's ``predict_path``).
+    ``predict_path`` keeps refusing mixed widths.  A backend without ``mmv_sigmas`` scores width by width.  The first
+    member's centre cache is used; a host model returns a host tensor for host rows, as ``predict`` does."""
+    estimators = list(estimators)
+    if not estimators:
+        raise ValueError("predict_grid: no estimators")
+    first = estimators[0]
+    for est in estimators:
+        if est.alpha_ is None or est.ny_points_ is None:
+            raise RuntimeError("predict_grid called before fit")
+        if not _same_tensor(est.ny_points_, first.ny_points_):
+            raise ValueError("predict_grid: the estimators must share one ny_points_ tensor (the members of a fit_grid do)")
+        if est.alpha_.dim() != 2 or tuple(est.alpha_.shape) != (first.ny_points_.shape[0], 1):
+            raise ValueError("predict_grid: every alpha_ must be (M, 1), got %s" % (tuple(est.alpha_.shape),))
+    sigmas = [float(est.kernel.sigma) for est in estimators]
+    V = torch.cat([est.alpha_ for est in estimators], dim=1)
+    be = _backend.get_backend()
+    F, Zf = be.features(X), first._centres()
+    if hasattr(be, "mmv_sigmas"):
+        res = be.mmv_sigmas(F, Zf, sigmas, V)
+    else:
+        res = torch.cat([be.mmv(F, Zf, s, V[:, t:t + 1].contiguous()) for t, s in enumerate(sigmas)], dim=1)
     if first._cpu_model and not (torch.is_tensor(X) and X.is_cuda):
         res = res.cpu()
     return res

@@ -16,6 +16,7 @@ ODX_OK = 0
 KNM_F32, KNM_U24, KNM_BF16 = 0, 1, 2
 KNM_CODE = {"f32": KNM_F32, "u24": KNM_U24, "bf16": KNM_BF16}      # Knm.fmt -> the ODX_KNM_* code of include/odx.h
 STREAM_MAX_VECTORS = 16      # ODX_STREAM_MAX_VECTORS: vectors one odx_gauss_ktk_stream_h2n call serves from one build of K
+GRID_MAX_SIGMAS = 4         # ODX_GRID_MAX_SIGMAS: kernel widths one odx_gauss_knm_h2_store_sigmas call builds from one contraction
 GEMM_LOWER_ONLY, GEMM_A_UPPER, GEMM_B_UPPER, GEMM_A_LOWER, GEMM_B_LOWER, GEMM_STORE_T = 1, 2, 4, 8, 16, 32
 
 
@@ -64,6 +65,12 @@ SIGNATURES = {
     "odx_gauss_mmvn_h2_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "odx_gauss_mmvn_h2": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _vp, _i64, _i32, _vp, _i64,
                                  _vp, _i64, _vp]),
+    "odx_gauss_mmvn_h2_sigmas_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "odx_gauss_mmvn_h2_sigmas": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i64,
+                                        _vp, _i64, _vp]),
+    "odx_gauss_knm_h2_store_sigmas_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "odx_gauss_knm_h2_store_sigmas": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp,
+                                             _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
     "odx_falkon_cg_workspace_bytes": (_i64, [_i64, _i64]),
     "odx_falkon_cg_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _f64, _i32, _i32, _f64, _f64, _vp, _vp,
                                  _i64, _vp]),

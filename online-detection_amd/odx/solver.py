@@ -405,6 +405,60 @@ def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=Non
     return _fit_members(be, K, [(P, lam, b0) for P, lam in zip(Ps, lams)], M, n, maxiter, opt, ar, ph)
 
 
+def falkon_fit_grid(be, F, y, Zf, sigmas, lams, maxiter=20, opt=None, n_total=None, allreduce=None, phase=None, blocks_at_once=4,
+                    knm_blocks=None):
+    """Fit one binary FALKON problem at every (sigma, lambda) of a grid: alphas (S, L, M) f64, alphas[s] bit for bit what
+    falkon_fit_path(be, F, y, Zf, sigmas[s], lams, ...) returns.
+
+    The contraction X Z' behind a K_nM block does not depend on sigma, so the blocks of a group of `blocks_at_once` widths
+    come from ONE contraction where the backend has knm_rhs_sigmas (HipBackend: on the split-f16 wide tile core; it loops
+    knm_rhs elsewhere, as this function does for a backend without the method).  Per group: one knm_rhs_sigmas (phase
+    "knm"); then, width by width, the preconditioners of the lambda path (be.precond_path), the summed right-hand side and
+    the L conjugate-gradient states over that width's block, exactly as falkon_fit_path runs them; a block is dropped before
+    the next width's fit starts.  The blocks of a group are resident TOGETHER: blocks_at_once * odx_knm_bytes(n, M, fmt) is
+    the caller's to budget (1 = one block at a time, no shared contraction).
+
+    lams as falkon_fit_path; sigmas a non-empty sequence of finite positive widths.  Replicated row shards through
+    `allreduce` as there.  knm_blocks (a list) receives every block, which keeps them all alive."""
+    opt = opt or SolverOptions()
+    sigmas, lams = [float(x) for x in sigmas], [float(x) for x in lams]
+    if not sigmas or any(not (math.isfinite(x) and x > 0.0) for x in sigmas):
+        raise ValueError("falkon_fit_grid: sigmas must be a non-empty sequence of finite positive widths, got %r" % (sigmas,))
+    if not lams or any(not (math.isfinite(x) and x > 0.0) for x in lams):
+        raise ValueError("falkon_fit_grid: lams must be a non-empty sequence of finite positive penalties, got %r" % (lams,))
+    width = int(blocks_at_once)
+    if width < 1:
+        raise ValueError("falkon_fit_grid: blocks_at_once must be at least 1, got %r" % (blocks_at_once,))
+    S, L = len(sigmas), len(lams)
+    n = float(F.n if n_total is None else n_total)
+    M = Zf.n
+    ar = allreduce if allreduce is not None else (lambda v: v)
+    ph = phase if phase is not None else (lambda name: _NoPhase())
+    w = y * (1.0 / n)
+    alphas = be.zeros(S * L * M).view(S, L, M)
+    for s0 in range(0, S, width):
+        grp = sigmas[s0:s0 + width]
+        with ph("knm"):
+            if hasattr(be, "knm_rhs_sigmas"):
+                built = list(be.knm_rhs_sigmas(F, Zf, grp, w))
+            else:
+                built = [be.knm_rhs(F, Zf, sigma, w) for sigma in grp]
+        for i, sigma in enumerate(grp):
+            K, b0 = built[i]
+            built[i] = None                                  # this width's block goes with its fit
+            with ph("precond"):
+                if hasattr(be, "precond_path"):
+                    Ps = be.precond_path(Zf, sigma, lams, opt.pc_epsilon)
+                else:
+                    Ps = [be.precond(Zf, sigma, lam, opt.pc_epsilon) for lam in lams]
+            if knm_blocks is not None:
+                knm_blocks.append(K)
+            b0 = ar(b0)                                      # K' (y / n), summed over shards
+            alphas[s0 + i].copy_(_fit_members(be, K, [(P, lam, b0) for P, lam in zip(Ps, lams)], M, n, maxiter, opt, ar, ph))
+            del K, b0, Ps
+    return alphas
+
+
 def _fit_members(be, K, members, M, n, maxiter, opt, ar, ph, B0=None):
     """The L conjugate-gradient states (P, lam, b0) of `members` over ONE block K in lock step: the driver falkon_fit_path (one
     P per lambda, one b0) and falkon_fit_multi (one P and lambda, one b0 per label column: B0, the (L, Mp) matrix the b0 are
