@@ -19,6 +19,7 @@
 //          LDS rows, double-buffered (2 x 64 KiB), one barrier per stage, one workgroup per CU: half the L2 traffic
 //          per product.
 #include <stdlib.h>
+#include <type_traits>
 #include "gemm_core.h"
 #include "odx_internal.h"
 
@@ -374,18 +375,40 @@ __device__ __forceinline__ void s16_zero(f32x4 (&acc)[4][4]) {
     for (int tn = 0; tn < 4; ++tn) acc[tm][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// The tile (i0, j0) of a K_nM build's workgroup; false = a row block past the end of the last band.  The tiles run in bands
+// of `gr` row blocks: inside an XCD's run of workgroups (xcd_remap) the row blocks of a band take one column position after
+// the other, so a Z tile is shared in L2 by the row blocks of the band and the X panel of a row block by its columns.
+template <int BM, int BN>
+__device__ __forceinline__ bool knm_place(int gr, int64_t n, int64_t M, int64_t& i0, int64_t& j0) {
+  const int64_t GR = gr;
+  const int64_t tiles_n = (M + BN - 1) / BN;
+  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t band = wg / (GR * tiles_n), within = wg % (GR * tiles_n);
+  i0 = (band * GR + within % GR) * BM, j0 = (within / GR) * BN;
+  return i0 < n;
+}
+
+// The f64 reduce-scatter butterfly of the scoring kernels over the 16 lanes of a lane quarter (bits b8 b4 b2 b1 of the lane
+// number).  A lane holds the sums over its columns of 16 row slots; a stage leaves it the half of its values that its bit
+// selects, each added to the partner lane's.  QUARTER_STAGE is one stage for one pair (lo, hi): the first stage takes slots j
+// and j + 8 as they are formed (w8[j]); QUARTER_STAGES_4_2 declares w4 and w2, the stages 4 and 2 of those eight; stage 1 of
+// w2[0], w2[1] is the quarter's sum of slot l & 15 in lane l.  Every scoring kernel is held bit for bit to the others
+// through the order of selects, shuffles and additions here.  (Macros, not functions: as inlined functions the same
+// operations left the per-class and per-column kernels with other instruction streams than they had.)
+#define QUARTER_STAGE(b, lo, hi, off) (((b) ? (hi) : (lo)) + __shfl_xor((b) ? (lo) : (hi), off))
+#define QUARTER_STAGES_4_2(w8)                                                                  \
+  double w4[4], w2[2];                                                                          \
+  _Pragma("unroll") for (int j = 0; j < 4; ++j) w4[j] = QUARTER_STAGE(b4, w8[j], w8[j + 4], 4); \
+  _Pragma("unroll") for (int j = 0; j < 2; ++j) w2[j] = QUARTER_STAGE(b2, w4[j], w4[j + 2], 2)
+
 // accumulator element (tm, tn, q) of a wave's 64 x 64 share: row 16 tm + 4 (lane >> 4) + q, column 16 tn + (lane & 15)
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_knm_h2s16_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
     int ktiles, float gamma_log2e, float* __restrict__ K, int64_t ldk, int gr) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int64_t GR = gr;
-  const int64_t tiles_n = (M + GEMM_BN - 1) / GEMM_BN;
-  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t band = wg / (GR * tiles_n), within = wg % (GR * tiles_n);
-  const int64_t i0 = (band * GR + within % GR) * GEMM_BM, j0 = (within / GR) * GEMM_BN;
-  if (i0 >= n) return;
+  int64_t i0, j0;
+  if (!knm_place<GEMM_BM, GEMM_BN>(gr, n, M, i0, j0)) return;
 
   // (epilogue as in gauss_knm_h2w256_kernel: exponent formed already scaled from norms pre-multiplied by gamma log2(e), pad
   // columns through exp2(-inf) = 0, store addresses advanced by the row pitch instead of a 64-bit product per store)
@@ -453,7 +476,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmv_h2s16_kernel(
 
   if (threadIdx.x < GEMM_BM) xg_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] * gamma_log2e : 0.f;
   // Lane l ends every tile with the f64 sum over the tile's 64 columns of this wave of row slot (l & 15) of its lane
-  // quarter (slot = 4 tm + q, row 16 tm + 4 (l >> 4) + q): a reduce-scatter butterfly over the 16 lanes of the quarter.
+  // quarter (slot = 4 tm + q, row 16 tm + 4 (l >> 4) + q): see QUARTER_STAGE.
   double tot = 0.0;
   const bool b8 = lane & 8, b4 = lane & 4, b2 = lane & 2, b1 = lane & 1;
 
@@ -485,14 +508,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmv_h2s16_kernel(
           v[u] = fma((double)__builtin_amdgcn_exp2f(e), al[tn], v[u]);
         }
       }
-      w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+      w8[j] = QUARTER_STAGE(b8, v[0], v[1], 8);
     }
-    double w4[4], w2[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
-    tot += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+    QUARTER_STAGES_4_2(w8);
+    tot += QUARTER_STAGE(b1, w2[0], w2[1], 1);
   }
   {
     const int slot = lane & 15;
@@ -540,14 +559,27 @@ __device__ __forceinline__ void mmvn_fresh(f32x4 (&acc)[TM][4]) {
 // and then weighed by one column after the other.  Per column the f64 operations and their order (the fma chain over tn,
 // the butterflies, the sum over the tiles, the two halves in `red`, the slab) are those of gauss_mmv_h2s16_kernel with the
 // range [0, M): the same bits.  Columns past T (the padding of a group narrower than NV) weigh 0 and are not stored.
-template <int NV>
+//
+// PERCOL (odx_gauss_mmvn_h2_sigmas, the members of a (sigma, lambda) grid): a kernel width per column.  The accumulators
+// then keep what does not depend on sigma — the raw product here, whose form pre-scales the norms by gamma; the clamped d^2
+// in the wide kernel's form — and every column forms its entries with its own exponent, by the per-column kernels' own
+// expressions (gauss_mmv_h2s16_kernel / gauss_mmv_h2w256_kernel): column c is bit for bit the per-column launch with
+// sigma_c.  The price is NV times the exps (64 / 128 v_exp_f32 per lane, column and tile).  A launch's scaled exponents
+// gamma log2(e) come by value: one group of up to 8 columns with PERCOL (padding columns repeat the last one), g[0] for every
+// column without.  Per width every constant is formed by single f32 operations (no contraction into a neighbouring add).
+struct MmvnGammas {
+  float g[8];
+};
+
+template <int NV, bool PERCOL>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
-    int ktiles, float gamma_log2e, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
+    int ktiles, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
     double* __restrict__ slab, int64_t slab_ld) {
+#pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  __shared__ __attribute__((aligned(16))) float xg_s[GEMM_BM];      // row norms times gamma log2(e)
+  __shared__ __attribute__((aligned(16))) float xg_s[PERCOL ? NV : 1][GEMM_BM];      // row norms times (each column's) gamma log2(e)
   constexpr int64_t GR = 8;
   const int c0 = cbase + (int)blockIdx.y * NV;
   const int nc = T - c0 < NV ? T - c0 : NV;
@@ -560,9 +592,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
   if (i0 >= n || s0 >= M) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const float m2g = -2.f / (metax[0] * metaz[0]) * gamma_log2e;
+  const float m2 = -2.f / (metax[0] * metaz[0]);
 
-  if (threadIdx.x < GEMM_BM) xg_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] * gamma_log2e : 0.f;
+  if (threadIdx.x < GEMM_BM) {
+    const bool in = i0 + threadIdx.x < n;
+    const float xq = in ? xsq[i0 + threadIdx.x] : 0.f;
+#pragma unroll
+    for (int c = 0; c < (PERCOL ? NV : 1); ++c) xg_s[c][threadIdx.x] = in ? xq * gm.g[c] : 0.f;
+  }
   double tot[NV];
 #pragma unroll
   for (int c = 0; c < NV; ++c) tot[c] = 0.0;
@@ -571,31 +608,40 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
   for (int64_t j0 = s0; j0 < s1; j0 += GEMM_BN) {
     f32x4 acc[4][4];
     s16_zero(acc);
-    s16_mainloop(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, ktiles, lds);
-    float zs[4];
+    s16_mainloop(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, ktiles, lds);     // its barriers also publish xg_s
+    float zq[4];                        // column norms; without PERCOL: times gamma log2(e) already
     int64_t voff[4];                    // < 0: a column past the group / M (weight 0)
 #pragma unroll
     for (int tn = 0; tn < 4; ++tn) {
       const int64_t col = j0 + wc * 64 + tn * 16 + (lane & 15);
       const bool cv = col < s1;
-      zs[tn] = cv ? zsq[col] * gamma_log2e : 0.f;
+      zq[tn] = cv ? (PERCOL ? zsq[col] : zsq[col] * gm.g[0]) : 0.f;
       voff[tn] = cv ? col * ldv + c0 : -1;
     }
+    if (!PERCOL) {
+      const float m2g = m2 * gm.g[0];
 #pragma unroll
-    for (int tm = 0; tm < 4; ++tm)
+      for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float xs = xg_s[wr * 64 + tm * 16 + 4 * (lane >> 4) + q];
+        for (int q = 0; q < 4; ++q) {
+          const float xs = xg_s[0][wr * 64 + tm * 16 + 4 * (lane >> 4) + q];
 #pragma unroll
-        for (int tn = 0; tn < 4; ++tn)      // gamma < 0: d^2 >= 0 <=> e <= 0
-          acc[tm][tn][q] = __builtin_amdgcn_exp2f(fminf(fmaf(m2g, acc[tm][tn][q], xs) + zs[tn], 0.f));
-      }
+          for (int tn = 0; tn < 4; ++tn)      // gamma < 0: d^2 >= 0 <=> e <= 0
+            acc[tm][tn][q] = __builtin_amdgcn_exp2f(fminf(fmaf(m2g, acc[tm][tn][q], xs) + zq[tn], 0.f));
+        }
+    }
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       mmvn_fresh(acc);
+      const float gc = gm.g[c];
+      const float m2g = m2 * gc;
+      float zs[4];
       double al[4];
 #pragma unroll
-      for (int tn = 0; tn < 4; ++tn) al[tn] = (voff[tn] >= 0 && c < nc) ? V[voff[tn] + c] : 0.0;
+      for (int tn = 0; tn < 4; ++tn) {
+        zs[tn] = voff[tn] >= 0 ? zq[tn] * gc : 0.f;
+        al[tn] = (voff[tn] >= 0 && c < nc) ? V[voff[tn] + c] : 0.0;
+      }
       double w8[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {       // slots j (tm = j >> 2) and j + 8 (tm = 2 + (j >> 2)), q = j & 3
@@ -603,18 +649,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int tm = 2 * u + (j >> 2), q = j & 3;
+          const float xs = xg_s[PERCOL ? c : 0][wr * 64 + tm * 16 + 4 * (lane >> 4) + q];
           v[u] = 0.0;
 #pragma unroll
-          for (int tn = 0; tn < 4; ++tn) v[u] = fma((double)acc[tm][tn][q], al[tn], v[u]);
+          for (int tn = 0; tn < 4; ++tn) {
+            const float e = fminf(fmaf(m2g, acc[tm][tn][q], xs) + zs[tn], 0.f);
+            v[u] = fma((double)(PERCOL ? __builtin_amdgcn_exp2f(e) : acc[tm][tn][q]), al[tn], v[u]);
+          }
         }
-        w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+        w8[j] = QUARTER_STAGE(b8, v[0], v[1], 8);
       }
-      double w4[4], w2[2];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
-      tot[c] += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+      QUARTER_STAGES_4_2(w8);
+      tot[c] += QUARTER_STAGE(b1, w2[0], w2[1], 1);
     }
   }
   __syncthreads();                            // every wave is done with the operand images: `red` takes their place
@@ -1190,12 +1236,8 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_knm_h2w256_kernel(
     int stages, float gamma_log2e, void* __restrict__ Kp, int64_t ldk, unsigned char* __restrict__ Klo, int64_t ldlo, int gr,
     const double* __restrict__ w, double* __restrict__ wslab, int64_t wslab_ld) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int64_t GR = gr;
-  const int64_t tiles_n = (M + W_BN - 1) / W_BN;
-  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t band = wg / (GR * tiles_n), within = wg % (GR * tiles_n);
-  const int64_t i0 = (band * GR + within % GR) * W_BM, j0 = (within / GR) * W_BN;
-  if (i0 >= n) return;
+  int64_t i0, j0;
+  if (!knm_place<W_BM, W_BN>(gr, n, M, i0, j0)) return;
 
   __shared__ __attribute__((aligned(16))) float xg_s[W_BM];
   __shared__ double ws_s[RHS ? W_BM : 1];
@@ -1262,12 +1304,8 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_knm_sigmas_h2w256_kernel(
     int stages, int S, KnmSigmaArgs sg, int64_t ldk, int64_t ldlo, int gr, const double* __restrict__ w, int64_t wslab_ld) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int64_t GR = gr;
-  const int64_t tiles_n = (M + W_BN - 1) / W_BN;
-  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t band = wg / (GR * tiles_n), within = wg % (GR * tiles_n);
-  const int64_t i0 = (band * GR + within % GR) * W_BM, j0 = (within / GR) * W_BN;
-  if (i0 >= n) return;
+  int64_t i0, j0;
+  if (!knm_place<W_BM, W_BN>(gr, n, M, i0, j0)) return;
 
   __shared__ __attribute__((aligned(16))) float xg_s[ODX_GRID_MAX_SIGMAS][W_BM];      // row norms times each width's gamma log2(e)
   __shared__ double ws_s[RHS ? W_BM : 1];
@@ -1940,14 +1978,10 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmv_h2w256_kernel(
             v[u] = fma((double)__builtin_amdgcn_exp2f(d2 * gamma_log2e), al[tn], v[u]);
           }
         }
-        w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+        w8[j] = QUARTER_STAGE(b8, v[0], v[1], 8);
       }
-      double w4[4], w2[2];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
-      tot[h] += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+      QUARTER_STAGES_4_2(w8);
+      tot[h] += QUARTER_STAGE(b1, w2[0], w2[1], 1);
     }
   }
   {
@@ -1969,12 +2003,15 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmv_h2w256_kernel(
 // accumulators, then today's weighted sum and butterflies run once per column of the group.  Same f64 operations in the
 // same order per column as gauss_mmv_h2w256_kernel with the range [0, M).  The accumulators stay live through all NV
 // columns (there they die as they are read), so the column sums are kept out of the registers: see `park` and `mine`.
-template <int NV, int CORE>
+// PERCOL: a kernel width per column (see gauss_mmvn_h2s16_kernel): the accumulators become the clamped squared distances,
+// the part of an entry every width shares, and each column takes its own exp2.
+template <int NV, int CORE, bool PERCOL>
 __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_h2w256_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
-    int stages, float gamma_log2e, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
+    int stages, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
     double* __restrict__ slab, int64_t slab_ld) {
+#pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ __attribute__((aligned(16))) float xs_s[W_BM];
   // The sums of the first PARK columns stay in LDS of their own for the whole kernel: 3 x 8 KiB is what the CU has left
@@ -2036,129 +2073,7 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_h2w256_kernel(
         for (int tn = 0; tn < 4; ++tn) {    // (the form of gauss_mmv_h2w256_kernel: its bits are the contract)
           float d2 = fmaf(m2, acc[tm][tn][q], xs) + zs[tn];
           d2 = fmaxf(d2, 0.f);
-          acc[tm][tn][q] = __builtin_amdgcn_exp2f(d2 * gamma_log2e);
-        }
-      }
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      mmvn_fresh(acc);
-      double al[4];
-#pragma unroll
-      for (int tn = 0; tn < 4; ++tn) al[tn] = (col0 + 16 * tn < s1 && c < nc) ? vp[16 * tn * ldv + c] : 0.0;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        double w8[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {       // slots j (tm' = j >> 2) and j + 8 (tm' = 2 + (j >> 2)), q = j & 3
-          double v[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int tm = 4 * h + 2 * u + (j >> 2), q = j & 3;
-            v[u] = 0.0;
-#pragma unroll
-            for (int tn = 0; tn < 4; ++tn) v[u] = fma((double)acc[tm][tn][q], al[tn], v[u]);
-          }
-          w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
-        }
-        double w4[4], w2[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
-        double* sum = c < PARK ? parked + c * 4 * W_BM + 64 * h : mine + (c - PARK) * 4 * W_BM + 64 * h;
-        *sum += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
-      }
-    }
-    if (j0 + W_BN < s1) {
-#pragma unroll
-      for (int c = 0; c < NV - PARK; ++c) tot[c][0] = mine[c * 4 * W_BM], tot[c][1] = mine[c * 4 * W_BM + 64];
-    }
-    __syncthreads();                  // the next main loop writes the images at once; behind the last tile: `red` is complete
-  }
-  if (threadIdx.x < W_BM) {
-    const int64_t row = i0 + threadIdx.x;
-    if (row < n)
-      for (int c = 0; c < nc; ++c) {
-        const double* rc = (c < PARK ? &park[0][0][0] + c * 4 * W_BM : red + (c - PARK) * 4 * W_BM) + threadIdx.x;
-        slab[((int64_t)(c0 + c) * G + g) * slab_ld + row] = (rc[0] + rc[W_BM]) + (rc[2 * W_BM] + rc[3 * W_BM]);
-      }
-  }
-}
-
-// ---- shared-centre scoring with a kernel width PER COLUMN (odx_gauss_mmvn_h2_sigmas): the members of a (sigma, lambda) grid
-// The two kernels above write a tile's entries over the accumulators once and weigh them NV times.  With a width per column
-// the accumulators keep instead what does not depend on sigma — the clamped d^2 in the wide kernel's form, the raw product
-// in the s16 kernel's, whose form pre-scales the norms by gamma — and every column forms its entries with its own exponent,
-// by the per-column kernels' own expressions (gauss_mmv_h2w256_kernel / gauss_mmv_h2s16_kernel): column c is bit for bit
-// the per-column launch with sigma_c.  The price is NV times the exps (128 / 64 v_exp_f32 per lane, column and tile).  One
-// launch serves one group of up to 8 columns, whose scaled exponents come by value (padding columns repeat the last one).
-struct MmvnGammas {
-  float g[8];
-};
-
-template <int NV, int CORE>
-__global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_sigmas_h2w256_kernel(
-    const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
-    const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
-    int stages, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
-    double* __restrict__ slab, int64_t slab_ld) {
-#pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  __shared__ __attribute__((aligned(16))) float xs_s[W_BM];
-  constexpr int PARK = NV < 3 ? NV : 3;                // (see gauss_mmvn_h2w256_kernel)
-  __shared__ double park[PARK][4][W_BM];
-  constexpr int64_t GR = 8;
-  const int c0 = cbase + (int)blockIdx.y * NV;
-  const int nc = T - c0 < NV ? T - c0 : NV;
-  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t band = wg / (GR * G), within = wg % (GR * G);
-  const int64_t i0 = (band * GR + within % GR) * W_BM;
-  const int g = (int)(within / GR);
-  const int64_t s0 = (int64_t)g * tg * W_BN;
-  const int64_t s1 = (s0 + (int64_t)tg * W_BN < M) ? s0 + (int64_t)tg * W_BN : M;
-  if (i0 >= n || s0 >= M) return;
-  const float m2 = -2.f / (metax[0] * metaz[0]);
-  double* red = reinterpret_cast<double*>(lds);       // [NV][4 (wc)][W_BM], over the operand images (w_mainloop_dma ends on a barrier)
-
-  if (threadIdx.x < W_BM) xs_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] : 0.f;
-  double tot[NV - PARK + 1][2];           // (+ 1: no empty array at NV = 2)
-#pragma unroll
-  for (int c = 0; c < NV - PARK; ++c) tot[c][0] = tot[c][1] = 0.0;
-  {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* mine = &park[0][wave & 3][(wave >> 2) * 128 + 16 * ((lane & 15) >> 2) + 4 * (lane >> 4) + (lane & 3)];
-#pragma unroll
-    for (int c = 0; c < PARK; ++c) mine[c * 4 * W_BM] = mine[c * 4 * W_BM + 64] = 0.0;
-  }
-
-  for (int64_t j0 = s0; j0 < s1; j0 += W_BN) {
-    f32x4 acc[8][4];
-    w_zero(acc);
-    w_mainloop_dma<false, CORE>(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, stages, lds);
-    int tid = threadIdx.x;                              // (derived here, opaquely: see gauss_mmvn_h2w256_kernel)
-    asm volatile("" : "+v"(tid));
-    const int lane = tid & 63, wr = tid >> 8, wc = (tid >> 6) & 3;
-    const bool b8 = lane & 8, b4 = lane & 4, b2 = lane & 2, b1 = lane & 1;
-    const int slot = wc * W_BM + wr * 128 + 16 * ((lane & 15) >> 2) + 4 * (lane >> 4) + (lane & 3);
-    double* mine = red + slot;
-    double* parked = &park[0][0][0] + slot;
-#pragma unroll
-    for (int c = 0; c < NV - PARK; ++c) mine[c * 4 * W_BM] = tot[c][0], mine[c * 4 * W_BM + 64] = tot[c][1];
-    float zs[4];
-    const int64_t col0 = j0 + wc * 64 + (lane & 15);       // this lane's columns: col0 + 16 tn; past the group / M: weight 0
-    const double* vp = V + col0 * ldv + c0;
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn) zs[tn] = col0 + 16 * tn < s1 ? zsq[col0 + 16 * tn] : 0.f;
-    // the accumulators become the clamped squared distances: the part of an entry every width shares
-#pragma unroll
-    for (int tm = 0; tm < 8; ++tm)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float xs = xs_s[wr * 128 + tm * 16 + 4 * (lane >> 4) + q];
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn) {
-          const float d2 = fmaf(m2, acc[tm][tn][q], xs) + zs[tn];
-          acc[tm][tn][q] = fmaxf(d2, 0.f);
+          acc[tm][tn][q] = PERCOL ? d2 : __builtin_amdgcn_exp2f(d2 * gm.g[0]);
         }
       }
 #pragma unroll
@@ -2179,17 +2094,14 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_sigmas_h2w256_kernel(
             const int tm = 4 * h + 2 * u + (j >> 2), q = j & 3;
             v[u] = 0.0;
 #pragma unroll
-            for (int tn = 0; tn < 4; ++tn) v[u] = fma((double)__builtin_amdgcn_exp2f(acc[tm][tn][q] * gc), al[tn], v[u]);
+            for (int tn = 0; tn < 4; ++tn)
+              v[u] = fma((double)(PERCOL ? __builtin_amdgcn_exp2f(acc[tm][tn][q] * gc) : acc[tm][tn][q]), al[tn], v[u]);
           }
-          w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
+          w8[j] = QUARTER_STAGE(b8, v[0], v[1], 8);
         }
-        double w4[4], w2[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
+        QUARTER_STAGES_4_2(w8);
         double* sum = c < PARK ? parked + c * 4 * W_BM + 64 * h : mine + (c - PARK) * 4 * W_BM + 64 * h;
-        *sum += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
+        *sum += QUARTER_STAGE(b1, w2[0], w2[1], 1);
       }
     }
     if (j0 + W_BN < s1) {
@@ -2205,107 +2117,6 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_sigmas_h2w256_kernel(
         const double* rc = (c < PARK ? &park[0][0][0] + c * 4 * W_BM : red + (c - PARK) * 4 * W_BM) + threadIdx.x;
         slab[((int64_t)(c0 + c) * G + g) * slab_ld + row] = (rc[0] + rc[W_BM]) + (rc[2 * W_BM] + rc[3 * W_BM]);
       }
-  }
-}
-
-template <int NV>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_sigmas_h2s16_kernel(
-    const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
-    const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
-    int ktiles, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
-    double* __restrict__ slab, int64_t slab_ld) {
-#pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  __shared__ __attribute__((aligned(16))) float xg_s[NV][GEMM_BM];      // row norms times each column's gamma log2(e)
-  constexpr int64_t GR = 8;
-  const int c0 = cbase + (int)blockIdx.y * NV;
-  const int nc = T - c0 < NV ? T - c0 : NV;
-  const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t band = wg / (GR * G), within = wg % (GR * G);
-  const int64_t i0 = (band * GR + within % GR) * GEMM_BM;
-  const int g = (int)(within / GR);
-  const int64_t s0 = (int64_t)g * tg * GEMM_BN;
-  const int64_t s1 = (s0 + (int64_t)tg * GEMM_BN < M) ? s0 + (int64_t)tg * GEMM_BN : M;
-  if (i0 >= n || s0 >= M) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const float m2 = -2.f / (metax[0] * metaz[0]);
-
-  if (threadIdx.x < GEMM_BM) {
-    const bool in = i0 + threadIdx.x < n;
-    const float xq = in ? xsq[i0 + threadIdx.x] : 0.f;
-#pragma unroll
-    for (int c = 0; c < NV; ++c) xg_s[c][threadIdx.x] = in ? xq * gm.g[c] : 0.f;
-  }
-  double tot[NV];
-#pragma unroll
-  for (int c = 0; c < NV; ++c) tot[c] = 0.0;
-  const bool b8 = lane & 8, b4 = lane & 4, b2 = lane & 2, b1 = lane & 1;
-
-  for (int64_t j0 = s0; j0 < s1; j0 += GEMM_BN) {
-    f32x4 acc[4][4];
-    s16_zero(acc);
-    s16_mainloop(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, ktiles, lds);     // its barriers also publish xg_s
-    float zq[4];
-    int64_t voff[4];                    // < 0: a column past the group / M (weight 0)
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
-      const int64_t col = j0 + wc * 64 + tn * 16 + (lane & 15);
-      const bool cv = col < s1;
-      zq[tn] = cv ? zsq[col] : 0.f;
-      voff[tn] = cv ? col * ldv + c0 : -1;
-    }
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      mmvn_fresh(acc);
-      const float gc = gm.g[c];
-      const float m2g = m2 * gc;
-      float zs[4];
-      double al[4];
-#pragma unroll
-      for (int tn = 0; tn < 4; ++tn) {
-        zs[tn] = voff[tn] >= 0 ? zq[tn] * gc : 0.f;
-        al[tn] = (voff[tn] >= 0 && c < nc) ? V[voff[tn] + c] : 0.0;
-      }
-      double w8[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {       // slots j (tm = j >> 2) and j + 8 (tm = 2 + (j >> 2)), q = j & 3
-        double v[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int tm = 2 * u + (j >> 2), q = j & 3;
-          const float xs = xg_s[c][wr * 64 + tm * 16 + 4 * (lane >> 4) + q];
-          v[u] = 0.0;
-#pragma unroll
-          for (int tn = 0; tn < 4; ++tn) {
-            const float e = fminf(fmaf(m2g, acc[tm][tn][q], xs) + zs[tn], 0.f);     // gamma < 0: d^2 >= 0 <=> e <= 0
-            v[u] = fma((double)__builtin_amdgcn_exp2f(e), al[tn], v[u]);
-          }
-        }
-        w8[j] = (b8 ? v[1] : v[0]) + __shfl_xor(b8 ? v[0] : v[1], 8);
-      }
-      double w4[4], w2[2];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w4[j] = (b4 ? w8[j + 4] : w8[j]) + __shfl_xor(b4 ? w8[j] : w8[j + 4], 4);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) w2[j] = (b2 ? w4[j + 2] : w4[j]) + __shfl_xor(b2 ? w4[j] : w4[j + 2], 2);
-      tot[c] += (b1 ? w2[1] : w2[0]) + __shfl_xor(b1 ? w2[0] : w2[1], 1);
-    }
-  }
-  __syncthreads();                            // every wave is done with the operand images: `red` takes their place
-  double* red = reinterpret_cast<double*>(lds);       // [NV][2 (wr)][2 (wc)][64]
-  {
-    const int slot = lane & 15;
-#pragma unroll
-    for (int c = 0; c < NV; ++c) red[((c * 2 + wr) * 2 + wc) * 64 + (slot >> 2) * 16 + 4 * (lane >> 4) + (slot & 3)] = tot[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int w = threadIdx.x >> 6, rr = threadIdx.x & 63;
-    const int64_t row = i0 + w * 64 + rr;
-    if (row < n)
-      for (int c = 0; c < nc; ++c)
-        slab[((int64_t)(c0 + c) * G + g) * slab_ld + row] = red[((c * 2 + w) * 2 + 0) * 64 + rr] + red[((c * 2 + w) * 2 + 1) * 64 + rr];
   }
 }
 
@@ -2327,6 +2138,28 @@ static bool h2_use_w256(int64_t tiles256) {
   if (t == 128) return false;
   if (t == 256) return true;
   return tiles256 >= 512;
+}
+
+// the kernels' scaled exponent: exp(-d^2 / (2 sigma^2)) = exp2(d^2 gamma log2(e))
+static float h2_gamma_log2e(double sigma) { return (float)(-0.5 / (sigma * sigma)) * LOG2E; }
+
+// The pair of packed operands of a Gaussian entry `who`; dp: the least ld (4-byte units) its tile core reads.
+static int check_packed_pair(const char* who, int64_t dp, int64_t ldpx, int64_t ldpz, const void* PX, const void* PZ) {
+  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
+              "%s: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= %lld 4-byte units", who, (long long)dp);
+  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24), "%s: leading dimensions must stay below 2^24 (32-bit tile offsets)", who);
+  return ODX_OK;
+}
+
+// A stored K_nM block in format fmt (ODX_KNM_*) and, for the 24-bit format, its low-byte plane.
+static int check_knm_block(const char* who, int fmt, int64_t M, const void* K, int64_t ldk, const void* Klo, int64_t ldlo) {
+  const int64_t ldmin = odx_knm_ld(M, fmt);
+  ODX_REQUIRE(K && ldk >= ldmin && ldk % (fmt == ODX_KNM_F32 ? 4 : 8) == 0 && aligned16(K),
+              "%s: K must be 16-byte aligned with ldk a multiple of %d and >= %lld", who, fmt == ODX_KNM_F32 ? 4 : 8, (long long)ldmin);
+  if (fmt == ODX_KNM_U24)
+    ODX_REQUIRE(Klo && ldlo >= ldmin && ldlo % 8 == 0 && aligned16(Klo), "%s: the low-byte plane must be 16-byte aligned with ldlo %% 8 == 0, ldlo >= roundup(M, 8)", who);
+  ODX_REQUIRE(ldk < (1 << 24), "%s: leading dimensions must stay below 2^24 (32-bit tile offsets)", who);
+  return ODX_OK;
 }
 
 // (internal, odx_internal.h) packed bytes of a (rows x cols) f64 operand of gemm_h2_f64
@@ -2448,6 +2281,20 @@ extern "C" int odx_split_f16_premax(const float* X, int64_t ldx, int64_t n, int 
   return ODX_OK;
 }
 
+// The build instantiation for (w != nullptr, storage format): launch(RHS, FMT) gets the two as integral constants.
+static_assert(KF_F32 == ODX_KNM_F32 && KF_U24 == ODX_KNM_U24 && KF_BF16 == ODX_KNM_BF16, "the kernels' FMT is the interface's fmt");
+template <bool B> using BoolC = std::integral_constant<bool, B>;
+template <int I> using IntC = std::integral_constant<int, I>;
+template <typename L>
+static int knm_rhs_fmt(bool rhs, int kf, L&& launch) {
+  if (rhs) return kf == KF_F32 ? launch(BoolC<true>(), IntC<KF_F32>()) : kf == KF_U24 ? launch(BoolC<true>(), IntC<KF_U24>()) : launch(BoolC<true>(), IntC<KF_BF16>());
+  return kf == KF_F32 ? launch(BoolC<false>(), IntC<KF_F32>()) : kf == KF_U24 ? launch(BoolC<false>(), IntC<KF_U24>()) : launch(BoolC<false>(), IntC<KF_BF16>());
+}
+
+// the band height of the wide builds' tile order (2 / 4 / 8 / 16 / 32 measured alone: 395 / 397 / 391 / 376 / 347 TF) and their grid
+constexpr int W_KNM_GR = 4;
+static int64_t knm_w256_grid(int64_t n, int64_t M) { return round_up(ceil_div(n, W_BM), W_KNM_GR) * ceil_div(M, W_BN); }
+
 template <bool RHS, int FMT, int CORE>
 static int launch_knm_w256_t(unsigned wt, hipStream_t s, const uint32_t* PX, int64_t ldpx, const float* metax, const float* xsq,
                              int64_t n, const uint32_t* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M,
@@ -2465,32 +2312,20 @@ static int launch_knm_w256(const void* PX, int64_t ldpx, const float* metax, con
                            int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int stages, double sigma, int fmt,
                            void* K, int64_t ldk, void* Klo, int64_t ldlo, const double* w, double* wslab, int64_t wslab_ld,
                            odx_stream_t stream, int core = CORE_H2) {
-  // band height of the tile order; 2 / 4 / 8 / 16 / 32 measured alone: 395 / 397 / 391 / 376 / 347 TF
-  const int wgr = 4;
-  const int64_t wt = round_up(ceil_div(n, W_BM), wgr) * ceil_div(M, W_BN);
+  const int64_t wt = knm_w256_grid(n, M);
   ODX_REQUIRE(wt < (1ll << 31), "odx_gauss_knm_h2: grid too large");
-  const float g2 = (float)(-0.5 / (sigma * sigma)) * LOG2E;
+  const float g2 = h2_gamma_log2e(sigma);
   hipStream_t s = as_stream(stream);
   const uint32_t *px = (const uint32_t*)PX, *pz = (const uint32_t*)PZ;
   unsigned char* lo = static_cast<unsigned char*>(Klo);
-#define ODX_KNM_W256(RHS_, FMT_, CORE_)                                                                                        \
-  ODX_PROPAGATE((launch_knm_w256_t<RHS_, FMT_, CORE_>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages, \
-                                                      g2, K, ldk, lo, ldlo, wgr, w, wslab, wslab_ld)))
-#define ODX_KNM_W256_F(RHS_, CORE_)                     \
-  do {                                                  \
-    if (fmt == KF_F32) ODX_KNM_W256(RHS_, KF_F32, CORE_);      \
-    else if (fmt == KF_U24) ODX_KNM_W256(RHS_, KF_U24, CORE_); \
-    else ODX_KNM_W256(RHS_, KF_BF16, CORE_);                   \
-  } while (0)
-  if (core == CORE_F8) {
-    if (w != nullptr) ODX_KNM_W256_F(true, CORE_F8);
-    else ODX_KNM_W256_F(false, CORE_F8);
-  } else {
-    if (w != nullptr) ODX_KNM_W256_F(true, CORE_H2);
-    else ODX_KNM_W256_F(false, CORE_H2);
-  }
-#undef ODX_KNM_W256_F
-#undef ODX_KNM_W256
+  ODX_PROPAGATE(knm_rhs_fmt(w != nullptr, fmt, [&](auto rhs, auto kf) {
+    constexpr bool RHS = decltype(rhs)::value;
+    constexpr int FMT = decltype(kf)::value;
+    return core == CORE_F8 ? launch_knm_w256_t<RHS, FMT, CORE_F8>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages,
+                                                                  g2, K, ldk, lo, ldlo, W_KNM_GR, w, wslab, wslab_ld)
+                           : launch_knm_w256_t<RHS, FMT, CORE_H2>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages,
+                                                                  g2, K, ldk, lo, ldlo, W_KNM_GR, w, wslab, wslab_ld);
+  }));
   ODX_CHECK_LAUNCH("odx_gauss_knm_h2(w256)");
   return ODX_OK;
 }
@@ -2940,10 +2775,8 @@ extern "C" int odx_gauss_knm_h2(const void* PX, int64_t ldpx, const float* metax
   if (n <= 0 || M <= 0) return ODX_OK;
   ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && K && D > 0 && sigma > 0, "odx_gauss_knm_h2: bad argument");
   const int64_t dp = round_up(D, H2_KT);
-  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
-              "odx_gauss_knm_h2: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)");
-  ODX_REQUIRE(ldk % 4 == 0 && ldk >= round_up(M, 4) && aligned16(K), "odx_gauss_knm_h2: K must be 16-byte aligned, ldk %% 4 == 0, ldk >= roundup(M, 4)");
-  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24) && ldk < (1 << 24), "odx_gauss_knm_h2: leading dimensions must stay below 2^24 (32-bit tile offsets)");
+  ODX_PROPAGATE(check_packed_pair("odx_gauss_knm_h2", dp, ldpx, ldpz, PX, PZ));
+  ODX_PROPAGATE(check_knm_block("odx_gauss_knm_h2", ODX_KNM_F32, M, K, ldk, nullptr, 0));
   const int gr = 8;   // band height of the tile order: 2..32 measured within 2 % of each other at n = 2.5e5, M = 1e4
   if (h2_use_w256(ceil_div(n, W_BM) * ceil_div(M, W_BN)))
     return launch_knm_w256(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, (int)(dp / W_KS), sigma, KF_F32, K, ldk, nullptr, 0, nullptr, nullptr, 0, stream);
@@ -2952,7 +2785,7 @@ extern "C" int odx_gauss_knm_h2(const void* PX, int64_t ldpx, const float* metax
   ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_knm_h2s16_kernel)));
   hipLaunchKernelGGL(gauss_knm_h2s16_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), S16_LDS_BYTES, as_stream(stream),
                      (const uint32_t*)PX, ldpx, metax, xsq, n, (const uint32_t*)PZ, ldpz, metaz, zsq, M, (int)(dp / H2_KT),
-                     (float)(-0.5 / (sigma * sigma)) * LOG2E, K, ldk, gr);
+                     h2_gamma_log2e(sigma), K, ldk, gr);
   ODX_CHECK_LAUNCH("odx_gauss_knm_h2");
   return ODX_OK;
 }
@@ -2973,10 +2806,8 @@ extern "C" int odx_gauss_knm_h2_rhs(const void* PX, int64_t ldpx, const float* m
   }
   ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && K && w && D > 0 && sigma > 0, "odx_gauss_knm_h2_rhs: bad argument");
   const int64_t dp = round_up(D, H2_KT);
-  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
-              "odx_gauss_knm_h2_rhs: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)");
-  ODX_REQUIRE(ldk % 4 == 0 && ldk >= round_up(M, 4) && aligned16(K), "odx_gauss_knm_h2_rhs: K must be 16-byte aligned, ldk %% 4 == 0, ldk >= roundup(M, 4)");
-  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24) && ldk < (1 << 24), "odx_gauss_knm_h2_rhs: leading dimensions must stay below 2^24 (32-bit tile offsets)");
+  ODX_PROPAGATE(check_packed_pair("odx_gauss_knm_h2_rhs", dp, ldpx, ldpz, PX, PZ));
+  ODX_PROPAGATE(check_knm_block("odx_gauss_knm_h2_rhs", ODX_KNM_F32, M, K, ldk, nullptr, 0));
   if (workspace == nullptr || workspace_bytes < odx_gauss_knm_h2_rhs_workspace_bytes(n, M)) {
     set_error("odx_gauss_knm_h2_rhs: workspace too small");
     return ODX_ERR_WORKSPACE;
@@ -3014,22 +2845,14 @@ static int knm_store_impl(const char* who, int core, const void* PX, int64_t ldp
     return ODX_OK;
   }
   ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && K && D > 0 && sigma > 0, "%s: bad argument", who);
-  const int64_t dp = core_min_ld(D, core);
-  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
-              "%s: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= %lld 4-byte units", who, (long long)dp);
-  const int64_t ldmin = odx_knm_ld(M, fmt);
-  ODX_REQUIRE(ldk >= ldmin && ldk % (fmt == ODX_KNM_F32 ? 4 : 8) == 0 && aligned16(K),
-              "%s: K must be 16-byte aligned with ldk a multiple of %d and >= %lld", who, fmt == ODX_KNM_F32 ? 4 : 8, (long long)ldmin);
-  if (fmt == ODX_KNM_U24)
-    ODX_REQUIRE(Klo && ldlo >= ldmin && ldlo % 8 == 0 && aligned16(Klo), "%s: the low-byte plane must be 16-byte aligned with ldlo %% 8 == 0, ldlo >= roundup(M, 8)", who);
-  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24) && ldk < (1 << 24), "%s: leading dimensions must stay below 2^24 (32-bit tile offsets)", who);
+  ODX_PROPAGATE(check_packed_pair(who, core_min_ld(D, core), ldpx, ldpz, PX, PZ));
+  ODX_PROPAGATE(check_knm_block(who, fmt, M, K, ldk, Klo, ldlo));
   if (w != nullptr && (workspace == nullptr || workspace_bytes < odx_gauss_knm_h2_rhs_workspace_bytes(n, M))) {
     set_error("%s: workspace too small", who);
     return ODX_ERR_WORKSPACE;
   }
   const int64_t wld = round_up(M, 4);
-  const int kf = fmt == ODX_KNM_F32 ? KF_F32 : (fmt == ODX_KNM_U24 ? KF_U24 : KF_BF16);
-  ODX_PROPAGATE(launch_knm_w256(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, core_stages(D, core), sigma, kf, K, ldk, Klo, ldlo,
+  ODX_PROPAGATE(launch_knm_w256(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, core_stages(D, core), sigma, fmt, K, ldk, Klo, ldlo,
                                 w, static_cast<double*>(workspace), wld, stream, core));
   if (w == nullptr) return ODX_OK;
   return slab_reduce_f64(static_cast<const double*>(workspace), wld, (int)ceil_div(n, W_BM), M, ktw, as_stream(stream));
@@ -3075,19 +2898,12 @@ extern "C" int odx_gauss_knm_h2_store_sigmas(const void* PX, int64_t ldpx, const
   ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && D > 0, "%s: bad argument", who);
   ODX_REQUIRE(w == nullptr || (ktw != nullptr && ldktw >= M), "%s: w needs ktw with ldktw >= M", who);
   const int64_t dp = round_up(D, H2_KT);
-  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
-              "%s: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)", who);
-  const int64_t ldmin = odx_knm_ld(M, fmt);
-  ODX_REQUIRE(ldk >= ldmin && ldk % (fmt == ODX_KNM_F32 ? 4 : 8) == 0, "%s: ldk must be a multiple of %d and >= %lld", who,
-              fmt == ODX_KNM_F32 ? 4 : 8, (long long)ldmin);
-  if (fmt == ODX_KNM_U24) ODX_REQUIRE(ldlo >= ldmin && ldlo % 8 == 0, "%s: ldlo %% 8 == 0 and ldlo >= roundup(M, 8) needed", who);
-  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24) && ldk < (1 << 24), "%s: leading dimensions must stay below 2^24 (32-bit tile offsets)", who);
+  ODX_PROPAGATE(check_packed_pair(who, dp, ldpx, ldpz, PX, PZ));
   KnmSigmaArgs sg;
   for (int s = 0; s < ODX_GRID_MAX_SIGMAS; ++s) sg.g2[s] = 0.f, sg.K[s] = nullptr, sg.Klo[s] = nullptr, sg.wslab[s] = nullptr;
   for (int s = 0; s < S; ++s) {
-    ODX_REQUIRE(K[s] && aligned16(K[s]), "%s: block %d is null or not 16-byte aligned", who, s);
-    if (fmt == ODX_KNM_U24) ODX_REQUIRE(Klo[s] && aligned16(Klo[s]), "%s: low-byte plane %d is null or not 16-byte aligned", who, s);
-    sg.g2[s] = (float)(-0.5 / (sigmas[s] * sigmas[s])) * LOG2E;
+    ODX_PROPAGATE(check_knm_block(who, fmt, M, K[s], ldk, fmt == ODX_KNM_U24 ? Klo[s] : nullptr, ldlo));
+    sg.g2[s] = h2_gamma_log2e(sigmas[s]);
     sg.K[s] = K[s];
     sg.Klo[s] = fmt == ODX_KNM_U24 ? static_cast<unsigned char*>(Klo[s]) : nullptr;
   }
@@ -3099,25 +2915,15 @@ extern "C" int odx_gauss_knm_h2_store_sigmas(const void* PX, int64_t ldpx, const
   const int64_t wld = round_up(M, 4);
   if (w != nullptr)
     for (int s = 0; s < S; ++s) sg.wslab[s] = reinterpret_cast<double*>(static_cast<char*>(workspace) + s * per);
-  // the grid and the band height of launch_knm_w256: the same tile order
-  const int wgr = 4;
-  const int64_t wt = round_up(ceil_div(n, W_BM), wgr) * ceil_div(M, W_BN);
+  const int64_t wt = knm_w256_grid(n, M);             // launch_knm_w256's: the same tile order
   ODX_REQUIRE(wt < (1ll << 31), "%s: grid too large", who);
   hipStream_t hs = as_stream(stream);
   const uint32_t *px = (const uint32_t*)PX, *pz = (const uint32_t*)PZ;
   const int stages = (int)(dp / W_KS);
-#define ODX_KNM_SIG(RHS_, FMT_) \
-  ODX_PROPAGATE((launch_knm_sigmas_t<RHS_, FMT_>((unsigned)wt, hs, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages, S, sg, ldk, ldlo, wgr, w, wld)))
-#define ODX_KNM_SIG_F(RHS_)                          \
-  do {                                               \
-    if (fmt == ODX_KNM_F32) ODX_KNM_SIG(RHS_, KF_F32);      \
-    else if (fmt == ODX_KNM_U24) ODX_KNM_SIG(RHS_, KF_U24); \
-    else ODX_KNM_SIG(RHS_, KF_BF16);                        \
-  } while (0)
-  if (w != nullptr) ODX_KNM_SIG_F(true);
-  else ODX_KNM_SIG_F(false);
-#undef ODX_KNM_SIG_F
-#undef ODX_KNM_SIG
+  ODX_PROPAGATE(knm_rhs_fmt(w != nullptr, fmt, [&](auto rhs, auto kf) {
+    return launch_knm_sigmas_t<decltype(rhs)::value, decltype(kf)::value>((unsigned)wt, hs, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M,
+                                                                          stages, S, sg, ldk, ldlo, W_KNM_GR, w, wld);
+  }));
   ODX_CHECK_LAUNCH("odx_gauss_knm_h2_store_sigmas");
   if (w == nullptr) return ODX_OK;
   for (int s = 0; s < S; ++s)
@@ -3252,7 +3058,7 @@ static int launch_mmv_w256(const void* PX, int64_t ldpx, const float* metax, con
   ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmv_h2w256_kernel<CORE>), W_LDS_BYTES));
   hipLaunchKernelGGL((gauss_mmv_h2w256_kernel<CORE>), dim3((unsigned)wgs, (unsigned)C), dim3(W_THREADS), W_LDS_BYTES,
                      as_stream(stream), (const uint32_t*)PX, ldpx, metax, xsq, n, (const uint32_t*)PZ, ldpz, metaz, zsq, stages,
-                     (float)(-0.5 / (sigma * sigma)) * LOG2E, V, ldv, ranges, W_MMV_TG, (int)Gw, slab, slab_ld);
+                     h2_gamma_log2e(sigma), V, ldv, ranges, W_MMV_TG, (int)Gw, slab, slab_ld);
   ODX_CHECK_LAUNCH("odx_gauss_mmv(w256)");
   hipLaunchKernelGGL(mmv_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)C), dim3(256), 0, as_stream(stream), slab,
                      slab_ld, (int)Gw, W_MMV_TG, W_BN, ranges, n, out, ldo);
@@ -3268,10 +3074,8 @@ extern "C" int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax
   ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && ranges && out && D > 0 && sigma > 0 && ldv >= C && max_range > 0,
               "odx_gauss_mmv_h2: bad argument");
   const int64_t dp = round_up(D, H2_KT);
-  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
-              "odx_gauss_mmv_h2: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)");
+  ODX_PROPAGATE(check_packed_pair("odx_gauss_mmv_h2", dp, ldpx, ldpz, PX, PZ));
   ODX_REQUIRE(ldo >= C && C < 65536, "odx_gauss_mmv_h2: ldo < C or too many classes");
-  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24), "odx_gauss_mmv_h2: leading dimensions must stay below 2^24 (32-bit tile offsets)");
   if (workspace == nullptr || workspace_bytes < odx_gauss_mmv_h2_workspace_bytes(n, max_range, C)) {
     set_error("odx_gauss_mmv_h2: workspace too small");
     return ODX_ERR_WORKSPACE;
@@ -3288,7 +3092,7 @@ extern "C" int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax
   ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmv_h2s16_kernel)));
   hipLaunchKernelGGL(gauss_mmv_h2s16_kernel, dim3((unsigned)wgs, (unsigned)C), dim3(GEMM_THREADS), S16_LDS_BYTES,
                      as_stream(stream), (const uint32_t*)PX, ldpx, metax, xsq, n, (const uint32_t*)PZ, ldpz, metaz, zsq,
-                     (int)(dp / H2_KT), (float)(-0.5 / (sigma * sigma)) * LOG2E, V, ldv, ranges, tg, G, slab, slab_ld);
+                     (int)(dp / H2_KT), h2_gamma_log2e(sigma), V, ldv, ranges, tg, G, slab, slab_ld);
   ODX_CHECK_LAUNCH("odx_gauss_mmv_h2");
   hipLaunchKernelGGL(mmv_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)C), dim3(256), 0, as_stream(stream), slab,
                      slab_ld, G, tg, GEMM_BN, ranges, n, out, ldo);
@@ -3298,42 +3102,95 @@ extern "C" int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax
 
 // ---- shared-centre scoring: all T columns of a dense V from one evaluation of K per group of up to 8 columns
 struct MmvnArgs {
+  const char* who;
   const uint32_t *PX, *PZ;
   int64_t ldpx, ldpz, n, M, ldv, slab_ld;
   const float *metax, *xsq, *metaz, *zsq;
   const double* V;
   double* slab;
-  float gamma_log2e;
   int kt, T, tg, G;          // kt: k-tiles (128 x 128 core) or stages (256 x 256 core)
   unsigned wgs;
   hipStream_t stream;
 };
 
-template <int NV, bool WIDE>
-static int launch_mmvn_group(const MmvnArgs& a, int cbase, int groups) {
+// `groups` groups of NV columns from column cbase on
+template <int NV, bool WIDE, bool PERCOL>
+static int launch_mmvn_group(const MmvnArgs& a, const MmvnGammas& gm, int cbase, int groups) {
   if (WIDE) {
-    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2w256_kernel<NV, CORE_H2>), W_LDS_BYTES));
-    hipLaunchKernelGGL((gauss_mmvn_h2w256_kernel<NV, CORE_H2>), dim3(a.wgs, (unsigned)groups), dim3(W_THREADS), W_LDS_BYTES, a.stream,
-                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, a.gamma_log2e, a.V, a.ldv, cbase,
-                       a.T, a.tg, a.G, a.slab, a.slab_ld);
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2w256_kernel<NV, CORE_H2, PERCOL>), W_LDS_BYTES));
+    hipLaunchKernelGGL((gauss_mmvn_h2w256_kernel<NV, CORE_H2, PERCOL>), dim3(a.wgs, (unsigned)groups), dim3(W_THREADS), W_LDS_BYTES,
+                       a.stream, a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T,
+                       a.tg, a.G, a.slab, a.slab_ld);
   } else {
-    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2s16_kernel<NV>)));
-    hipLaunchKernelGGL((gauss_mmvn_h2s16_kernel<NV>), dim3(a.wgs, (unsigned)groups), dim3(GEMM_THREADS), S16_LDS_BYTES, a.stream,
-                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, a.gamma_log2e, a.V, a.ldv, cbase,
-                       a.T, a.tg, a.G, a.slab, a.slab_ld);
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2s16_kernel<NV, PERCOL>)));
+    hipLaunchKernelGGL((gauss_mmvn_h2s16_kernel<NV, PERCOL>), dim3(a.wgs, (unsigned)groups), dim3(GEMM_THREADS), S16_LDS_BYTES,
+                       a.stream, a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T,
+                       a.tg, a.G, a.slab, a.slab_ld);
   }
-  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2");
+  ODX_CHECK_LAUNCH(a.who);
   return ODX_OK;
 }
 
-// the full groups of 8 columns in one launch, what remains on the next instantiated width
+// one group of `rest` <= 8 columns on the next instantiated width
+template <bool WIDE, bool PERCOL>
+static int launch_mmvn_rest(const MmvnArgs& a, const MmvnGammas& gm, int cbase, int rest) {
+  if (rest > 4) return launch_mmvn_group<8, WIDE, PERCOL>(a, gm, cbase, 1);
+  if (rest > 2) return launch_mmvn_group<4, WIDE, PERCOL>(a, gm, cbase, 1);
+  return launch_mmvn_group<2, WIDE, PERCOL>(a, gm, cbase, 1);
+}
+
+// One width (sigmas == nullptr): the full groups of 8 columns in one launch, what remains in one more.  A width per column:
+// one launch per group of up to 8 columns, its scaled exponents by value (padding columns repeat the last one).
 template <bool WIDE>
-static int launch_mmvn(const MmvnArgs& a) {
-  const int full = a.T / 8, rest = a.T % 8;
-  if (full) ODX_PROPAGATE((launch_mmvn_group<8, WIDE>(a, 0, full)));
-  if (rest > 4) return launch_mmvn_group<8, WIDE>(a, 8 * full, 1);
-  if (rest > 2) return launch_mmvn_group<4, WIDE>(a, 8 * full, 1);
-  if (rest > 0) return launch_mmvn_group<2, WIDE>(a, 8 * full, 1);
+static int launch_mmvn(const MmvnArgs& a, double sigma, const double* sigmas) {
+  MmvnGammas gm;
+  if (sigmas == nullptr) {
+    for (int c = 0; c < 8; ++c) gm.g[c] = h2_gamma_log2e(sigma);
+    const int full = a.T / 8, rest = a.T % 8;
+    if (full) ODX_PROPAGATE((launch_mmvn_group<8, WIDE, false>(a, gm, 0, full)));
+    return rest ? launch_mmvn_rest<WIDE, false>(a, gm, 8 * full, rest) : ODX_OK;
+  }
+  for (int cbase = 0; cbase < a.T; cbase += 8) {
+    const int rest = a.T - cbase < 8 ? a.T - cbase : 8;
+    for (int c = 0; c < 8; ++c) gm.g[c] = h2_gamma_log2e(sigmas[cbase + (c < rest ? c : rest - 1)]);
+    ODX_PROPAGATE((launch_mmvn_rest<WIDE, true>(a, gm, cbase, rest)));
+  }
+  return ODX_OK;
+}
+
+// Both entries behind their own checks of the widths: the tile core, the groups of column tiles and the slab of
+// odx_gauss_mmv_h2 for T columns (the same bits per column), the launches, the sum of the groups.
+static int mmvn_run(const char* who, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
+                    int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma, const double* sigmas,
+                    const double* V, int64_t ldv, int T, float* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
+                    odx_stream_t stream) {
+  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && out && D > 0 && ldv >= T && M > 0, "%s: bad argument", who);
+  const int64_t dp = round_up(D, H2_KT);
+  ODX_PROPAGATE(check_packed_pair(who, dp, ldpx, ldpz, PX, PZ));
+  ODX_REQUIRE(ldo >= T && T < 65536, "%s: ldo < T or too many columns", who);
+  if (workspace == nullptr || workspace_bytes < odx_gauss_mmv_h2_workspace_bytes(n, M, T)) {
+    set_error("%s: workspace too small", who);
+    return ODX_ERR_WORKSPACE;
+  }
+  MmvnArgs a;
+  a.who = who, a.PX = (const uint32_t*)PX, a.PZ = (const uint32_t*)PZ, a.ldpx = ldpx, a.ldpz = ldpz, a.n = n, a.M = M, a.ldv = ldv;
+  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T;
+  a.slab = static_cast<double*>(workspace), a.slab_ld = round_up(n, 2), a.stream = as_stream(stream);
+  const bool wide = h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
+  int64_t wgs;
+  if (wide) {
+    a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = (int)(dp / W_KS);
+    wgs = round_up(ceil_div(n, W_BM), 8) * a.G;
+  } else {
+    a.tg = mmv_tg(n, M, T), a.G = (int)mmv_groups(M, a.tg), a.kt = (int)(dp / H2_KT);
+    wgs = round_up(ceil_div(n, GEMM_BM), 8) * a.G;
+  }
+  ODX_REQUIRE(wgs < (1ll << 31), "%s: grid too large", who);
+  a.wgs = (unsigned)wgs;
+  ODX_PROPAGATE(wide ? launch_mmvn<true>(a, sigma, sigmas) : launch_mmvn<false>(a, sigma, sigmas));
+  hipLaunchKernelGGL(mmvn_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)T), dim3(256), 0, a.stream, a.slab, a.slab_ld,
+                     a.G, n, out, ldo);
+  ODX_CHECK_LAUNCH(who);
   return ODX_OK;
 }
 
@@ -3346,73 +3203,9 @@ extern "C" int odx_gauss_mmvn_h2(const void* PX, int64_t ldpx, const float* meta
                                  const double* V, int64_t ldv, int T, float* out, int64_t ldo, void* workspace,
                                  int64_t workspace_bytes, odx_stream_t stream) {
   if (n <= 0 || T <= 0) return ODX_OK;
-  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && out && D > 0 && sigma > 0 && ldv >= T && M > 0,
-              "odx_gauss_mmvn_h2: bad argument");
-  const int64_t dp = round_up(D, H2_KT);
-  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
-              "odx_gauss_mmvn_h2: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)");
-  ODX_REQUIRE(ldo >= T && T < 65536, "odx_gauss_mmvn_h2: ldo < T or too many columns");
-  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24), "odx_gauss_mmvn_h2: leading dimensions must stay below 2^24 (32-bit tile offsets)");
-  if (workspace == nullptr || workspace_bytes < odx_gauss_mmvn_h2_workspace_bytes(n, M, T)) {
-    set_error("odx_gauss_mmvn_h2: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
-  MmvnArgs a;
-  a.PX = (const uint32_t*)PX, a.PZ = (const uint32_t*)PZ, a.ldpx = ldpx, a.ldpz = ldpz, a.n = n, a.M = M, a.ldv = ldv;
-  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T;
-  a.slab = static_cast<double*>(workspace), a.slab_ld = round_up(n, 2);
-  a.gamma_log2e = (float)(-0.5 / (sigma * sigma)) * LOG2E, a.stream = as_stream(stream);
-  // the tile core, the groups of column tiles and the slab of odx_gauss_mmv_h2 for T columns: the same bits per column
-  const bool wide = h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
-  int64_t wgs;
-  if (wide) {
-    a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = (int)(dp / W_KS);
-    wgs = round_up(ceil_div(n, W_BM), 8) * a.G;
-  } else {
-    a.tg = mmv_tg(n, M, T), a.G = (int)mmv_groups(M, a.tg), a.kt = (int)(dp / H2_KT);
-    wgs = round_up(ceil_div(n, GEMM_BM), 8) * a.G;
-  }
-  ODX_REQUIRE(wgs < (1ll << 31), "odx_gauss_mmvn_h2: grid too large");
-  a.wgs = (unsigned)wgs;
-  ODX_PROPAGATE(wide ? launch_mmvn<true>(a) : launch_mmvn<false>(a));
-  hipLaunchKernelGGL(mmvn_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)T), dim3(256), 0, a.stream, a.slab, a.slab_ld,
-                     a.G, n, out, ldo);
-  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2(reduce)");
-  return ODX_OK;
-}
-
-// ---- the same with a kernel width per column: one launch per group of up to 8 columns, its scaled exponents by value
-template <int NV, bool WIDE>
-static int launch_mmvn_sigmas_group(const MmvnArgs& a, const MmvnGammas& gm, int cbase) {
-  if (WIDE) {
-    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_sigmas_h2w256_kernel<NV, CORE_H2>), W_LDS_BYTES));
-    hipLaunchKernelGGL((gauss_mmvn_sigmas_h2w256_kernel<NV, CORE_H2>), dim3(a.wgs, 1u), dim3(W_THREADS), W_LDS_BYTES, a.stream,
-                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T, a.tg,
-                       a.G, a.slab, a.slab_ld);
-  } else {
-    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_sigmas_h2s16_kernel<NV>)));
-    hipLaunchKernelGGL((gauss_mmvn_sigmas_h2s16_kernel<NV>), dim3(a.wgs, 1u), dim3(GEMM_THREADS), S16_LDS_BYTES, a.stream,
-                       a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T, a.tg,
-                       a.G, a.slab, a.slab_ld);
-  }
-  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2_sigmas");
-  return ODX_OK;
-}
-
-template <bool WIDE>
-static int launch_mmvn_sigmas(const MmvnArgs& a, const double* sigmas) {
-  for (int cbase = 0; cbase < a.T; cbase += 8) {
-    const int rest = a.T - cbase < 8 ? a.T - cbase : 8;
-    MmvnGammas gm;
-    for (int c = 0; c < 8; ++c) {
-      const double sg = sigmas[cbase + (c < rest ? c : rest - 1)];
-      gm.g[c] = (float)(-0.5 / (sg * sg)) * LOG2E;
-    }
-    if (rest > 4) ODX_PROPAGATE((launch_mmvn_sigmas_group<8, WIDE>(a, gm, cbase)));
-    else if (rest > 2) ODX_PROPAGATE((launch_mmvn_sigmas_group<4, WIDE>(a, gm, cbase)));
-    else ODX_PROPAGATE((launch_mmvn_sigmas_group<2, WIDE>(a, gm, cbase)));
-  }
-  return ODX_OK;
+  ODX_REQUIRE(sigma > 0, "odx_gauss_mmvn_h2: bad argument");
+  return mmvn_run("odx_gauss_mmvn_h2", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, nullptr, V, ldv, T, out, ldo,
+                  workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t odx_gauss_mmvn_h2_sigmas_workspace_bytes(int64_t n, int64_t M, int T) {
@@ -3424,40 +3217,10 @@ extern "C" int odx_gauss_mmvn_h2_sigmas(const void* PX, int64_t ldpx, const floa
                                         const double* sigmas, const double* V, int64_t ldv, int T, float* out, int64_t ldo,
                                         void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
   if (n <= 0 || T <= 0) return ODX_OK;
-  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && out && sigmas && D > 0 && ldv >= T && M > 0,
-              "odx_gauss_mmvn_h2_sigmas: bad argument");
+  ODX_REQUIRE(sigmas, "odx_gauss_mmvn_h2_sigmas: bad argument");
   for (int c = 0; c < T; ++c) ODX_REQUIRE(sigmas[c] > 0, "odx_gauss_mmvn_h2_sigmas: sigma[%d] <= 0", c);
-  const int64_t dp = round_up(D, H2_KT);
-  ODX_REQUIRE(ldpx % 4 == 0 && ldpz % 4 == 0 && ldpx >= dp && ldpz >= dp && aligned16(PX) && aligned16(PZ),
-              "odx_gauss_mmvn_h2_sigmas: packed operands must be 16-byte aligned with ld %% 4 == 0 and ld >= roundup(D, 64)");
-  ODX_REQUIRE(ldo >= T && T < 65536, "odx_gauss_mmvn_h2_sigmas: ldo < T or too many columns");
-  ODX_REQUIRE(ldpx < (1 << 24) && ldpz < (1 << 24), "odx_gauss_mmvn_h2_sigmas: leading dimensions must stay below 2^24 (32-bit tile offsets)");
-  if (workspace == nullptr || workspace_bytes < odx_gauss_mmvn_h2_sigmas_workspace_bytes(n, M, T)) {
-    set_error("odx_gauss_mmvn_h2_sigmas: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
-  MmvnArgs a;
-  a.PX = (const uint32_t*)PX, a.PZ = (const uint32_t*)PZ, a.ldpx = ldpx, a.ldpz = ldpz, a.n = n, a.M = M, a.ldv = ldv;
-  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T;
-  a.slab = static_cast<double*>(workspace), a.slab_ld = round_up(n, 2);
-  a.gamma_log2e = 0.f, a.stream = as_stream(stream);
-  // the tile core, the groups of column tiles and the slab of odx_gauss_mmvn_h2 for T columns: the same bits per column
-  const bool wide = h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
-  int64_t wgs;
-  if (wide) {
-    a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = (int)(dp / W_KS);
-    wgs = round_up(ceil_div(n, W_BM), 8) * a.G;
-  } else {
-    a.tg = mmv_tg(n, M, T), a.G = (int)mmv_groups(M, a.tg), a.kt = (int)(dp / H2_KT);
-    wgs = round_up(ceil_div(n, GEMM_BM), 8) * a.G;
-  }
-  ODX_REQUIRE(wgs < (1ll << 31), "odx_gauss_mmvn_h2_sigmas: grid too large");
-  a.wgs = (unsigned)wgs;
-  ODX_PROPAGATE(wide ? launch_mmvn_sigmas<true>(a, sigmas) : launch_mmvn_sigmas<false>(a, sigmas));
-  hipLaunchKernelGGL(mmvn_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)T), dim3(256), 0, a.stream, a.slab, a.slab_ld,
-                     a.G, n, out, ldo);
-  ODX_CHECK_LAUNCH("odx_gauss_mmvn_h2_sigmas(reduce)");
-  return ODX_OK;
+  return mmvn_run("odx_gauss_mmvn_h2_sigmas", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, 0.0, sigmas, V, ldv, T, out, ldo,
+                  workspace, workspace_bytes, stream);
 }
 
 // Fused scoring with the e4m3 contraction (throughput-only, see odx_split_f8): always on the 256 x 256 core; workspace as
