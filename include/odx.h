@@ -196,6 +196,32 @@ int odx_gauss_mmvn_h2_sigmas(const void* PX, int64_t ldpx, const float* metax, c
                              const double* sigmas, const double* V, int64_t ldv, int T,
                              float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
+/* ---- Gaussian kernels on rows that are 16-bit already (bf16: is_bf16 = 1, f16: 0), at native width.
+ * Operands are those of odx_gemm_b16 at 64-element granularity: plain row-major 16-bit rows, 16-byte aligned, row strides ldx /
+ * ldz in ELEMENTS and multiples of 64 (one 128-byte stage), the columns D .. stride zero; no meta words, no scale.  A
+ * bf16 x bf16 or f16 x f16 product is exact in the f32 accumulator of one MFMA, so every entry is f32-accurate FOR THE ROWS
+ * AS GIVEN (the rounding to 16 bits is the caller's) at one matrix instruction per 32 features where the two-term split
+ * spends three, and nothing is packed.  xsq / zsq: odx_row_sqnorm_b16 (exact squares, summed in f32).
+ * odx_gauss_knm_b16_store  = odx_gauss_knm_h2_store   (wide 256 x 256 core; every storage format; fused K' w; same workspace)
+ * odx_gauss_mmv_b16        = odx_gauss_mmv_h2         (per-column centre ranges; both tile cores)
+ * odx_gauss_mmvn_b16       = odx_gauss_mmvn_h2        (dense V, 8 columns per evaluation of K; both tile cores)
+ * with the arguments, errors and workspaces of their siblings; the option h2_tile pins the tile core as it does there. */
+int odx_row_sqnorm_b16(const void* X, int64_t ldx, int64_t n, int D, int is_bf16, float* out, odx_stream_t stream);
+int64_t odx_gauss_knm_b16_store_workspace_bytes(int64_t n, int64_t M);
+int odx_gauss_knm_b16_store(const void* X, int64_t ldx, const float* xsq, int64_t n, const void* Z, int64_t ldz,
+                            const float* zsq, int64_t M, int D, int is_bf16, double sigma, int fmt, void* K, int64_t ldk,
+                            void* Klo, int64_t ldlo, const double* w, double* ktw, void* workspace,
+                            int64_t workspace_bytes, odx_stream_t stream);
+int64_t odx_gauss_mmv_b16_workspace_bytes(int64_t n, int64_t max_range, int T);
+int odx_gauss_mmv_b16(const void* X, int64_t ldx, const float* xsq, int64_t n, const void* Z, int64_t ldz, const float* zsq,
+                      int64_t max_range, int D, int is_bf16, double sigma, const double* V, int64_t ldv,
+                      const int32_t* ranges, int C, float* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
+                      odx_stream_t stream);
+int64_t odx_gauss_mmvn_b16_workspace_bytes(int64_t n, int64_t M, int T);
+int odx_gauss_mmvn_b16(const void* X, int64_t ldx, const float* xsq, int64_t n, const void* Z, int64_t ldz, const float* zsq,
+                       int64_t M, int D, int is_bf16, double sigma, const double* V, int64_t ldv, int T, float* out,
+                       int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+
 /* ---------------------------------------------------------------- A4: CG pass on stored K
  * falkon's incore_fdmmv on the stored K_nM (selected by store_kernel_d_threshold=250,
  * FALKONWrapper_with_centers_selection_incore.py:56):  out = K' (K v + w)  for one shard

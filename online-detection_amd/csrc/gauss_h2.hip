@@ -217,6 +217,11 @@ __device__ __forceinline__ void h2_load_operand(u32x4 (&r)[8], const uint32_t* _
   for (int p = 0; p < 8; ++p) r[p] = *reinterpret_cast<const u32x4*>(tile + voff[p]);
 }
 
+__device__ __forceinline__ void s16_clear_stage(H2Stage& st) {
+#pragma unroll
+  for (int p = 0; p < 8; ++p) st.a[p] = st.b[p] = u32x4{0u, 0u, 0u, 0u};
+}
+
 constexpr float LOG2E = 1.4426950408889634f;
 
 // ---------------------------------------------------------------- tile core
@@ -310,10 +315,15 @@ __device__ __forceinline__ void s16_tap_offsets(uint32_t (&off)[8], const uint32
 
 // TAPS: A is the 3 x 3 neighbourhood matrix of the packed NHWC rows at A (m rows of tapC channels + one all-zero row), gathered in
 // the operand loads as on the wide core (w_mainloop_dma): the eight row offsets of a lane are recomputed per k-tile.
-template <int CORE = S16_H2, bool PERMB = false, bool TAPS = false>
+// HALF (16-bit rows whose stride is a multiple of 64 features only, the Gaussian kernels' operand contract): with half_tail
+// the LAST k-tile holds 64 features — 128 bytes — per row, and the lanes of the upper eight 16-byte slots must not read
+// on into the next row (or past the operand's end).  They fetch the slot 128 bytes below their own instead, always inside
+// the row, and stage zeros: no branch around a load, nothing out of bounds, and zeros add nothing to a product.
+template <int CORE = S16_H2, bool PERMB = false, bool TAPS = false, bool HALF = false>
 __device__ __forceinline__ void s16_mainloop(f32x4 (&acc)[4][4], const uint32_t* __restrict__ A, int64_t lda, int64_t m,
                                              const uint32_t* __restrict__ B, int64_t ldb, int64_t n, int64_t i0, int64_t j0,
-                                             int ktiles, char* lds, int tapH = 0, int tapW = 0, int tapC = 0) {
+                                             int ktiles, char* lds, int tapH = 0, int tapW = 0, int tapC = 0, bool half_tail = false) {
+  static_assert(!HALF || (CORE != S16_H2 && !TAPS), "a half k-tile exists for plain 16-bit rows only");
   char* ldsA = lds;
   char* ldsB = lds + GEMM_BM * S16_ROW;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -339,16 +349,23 @@ __device__ __forceinline__ void s16_mainloop(f32x4 (&acc)[4][4], const uint32_t*
     h2_row_offsets<false>(offa, lda, i0, m);
   }
   H2Stage st;
+  const bool upper = HALF && half_tail && (threadIdx.x & 15) >= 8;      // this lane's slot does not exist in the last k-tile
+  const uint32_t back = upper ? 32u : 0u;                                // 4-byte units: the slot 128 bytes below
   if (TAPS) {
     uint32_t off[8];
     s16_tap_offsets(off, offa, hw, zoff, (int)lda, tapH, tapW, tc);
     h2_load_operand(st.a, ta, off);
+  } else if (HALF) {
+    const uint32_t bk = ktiles == 1 ? back : 0u;
+    h2_load_operand(st.a, ta - bk, offa);
+    h2_load_operand(st.b, tb - bk, offb);
   } else {
     h2_load_operand(st.a, ta, offa);
   }
-  h2_load_operand(st.b, tb, offb);
+  if (!HALF) h2_load_operand(st.b, tb, offb);
   for (int kt = 0; kt < ktiles; ++kt) {
     __syncthreads();
+    if (HALF && upper && kt + 1 == ktiles) s16_clear_stage(st);      // (what these lanes fetched for the last k-tile is not theirs)
     s16_store_operand(st.a, ldsA);
     s16_store_operand(st.b, ldsB);
     __syncthreads();
@@ -360,10 +377,14 @@ __device__ __forceinline__ void s16_mainloop(f32x4 (&acc)[4][4], const uint32_t*
       uint32_t off[8];
       s16_tap_offsets(off, offa, hw, zoff, (int)lda, tapH, tapW, tc);
       h2_load_operand(st.a, ta, off);
+    } else if (HALF) {
+      const uint32_t bk = kt + 2 >= ktiles ? back : 0u;      // the tile fetched here is the last one
+      h2_load_operand(st.a, ta + nk - bk, offa);
+      h2_load_operand(st.b, tb + nk - bk, offb);
     } else {
       h2_load_operand(st.a, ta + nk, offa);
     }
-    h2_load_operand(st.b, tb + nk, offb);
+    if (!HALF) h2_load_operand(st.b, tb + nk, offb);
     s16_compute_ktile<CORE>(acc, ldsA, ldsB, wr, wc, lane);
   }
 }
@@ -400,6 +421,14 @@ __device__ __forceinline__ bool knm_place(int gr, int64_t n, int64_t M, int64_t&
   double w4[4], w2[2];                                                                          \
   _Pragma("unroll") for (int j = 0; j < 4; ++j) w4[j] = QUARTER_STAGE(b4, w8[j], w8[j + 4], 4); \
   _Pragma("unroll") for (int j = 0; j < 2; ++j) w2[j] = QUARTER_STAGE(b2, w4[j], w4[j + 2], 2)
+
+// -2 / (s_x s_z) of a Gaussian epilogue.  The scales of the two-term splits (and of the e4m3 packing) are powers of two: exact.
+// Plain 16-bit rows (S16_BF16 / S16_F16, the wide core's CORE_BF16 / CORE_F16) carry no scale and no meta words.
+template <int CORE>
+__device__ __forceinline__ float core_m2(const float* __restrict__ metax, const float* __restrict__ metaz) {
+  if (CORE == S16_BF16 || CORE == S16_F16) return -2.f;
+  return -2.f / (metax[0] * metaz[0]);
+}
 
 // accumulator element (tm, tn, q) of a wave's 64 x 64 share: row 16 tm + 4 (lane >> 4) + q, column 16 tn + (lane & 15)
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_knm_h2s16_kernel(
@@ -452,11 +481,15 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_knm_h2s16_kernel(
 // XCD's run), so the X panel of a row block is shared in L2 by the groups working on it and a Z tile by the row blocks
 // of the band — one workgroup per row block walking all 79 column tiles re-fetched its 512-KB X panel for every tile
 // (458 GB of L2 misses per launch at n = 1e6, M = 1e4, against 132 GB for the build).
+// CORE S16_BF16 / S16_F16: PX / PZ are plain 16-bit rows (no meta), a k-tile is 128 features and `half_tail` says that the
+// last one holds 64 (s16_mainloop<.., HALF>).
+template <int CORE = S16_H2>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmv_h2s16_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int ktiles,
     float gamma_log2e, const double* __restrict__ V, int64_t ldv, const int32_t* __restrict__ ranges, int tg, int G,
-    double* __restrict__ slab, int64_t slab_ld) {
+    double* __restrict__ slab, int64_t slab_ld, int half_tail) {
+  constexpr bool B16 = CORE != S16_H2;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ double red[2][2][64];
   __shared__ __attribute__((aligned(16))) float xg_s[GEMM_BM];      // row norms times gamma log2(e)
@@ -472,7 +505,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmv_h2s16_kernel(
   if (i0 >= n || s0 >= r1) return;       // mmv_reduce_kernel only visits the groups that exist
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const float m2g = -2.f / (metax[0] * metaz[0]) * gamma_log2e;
+  const float m2g = core_m2<CORE>(metax, metaz) * gamma_log2e;
 
   if (threadIdx.x < GEMM_BM) xg_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] * gamma_log2e : 0.f;
   // Lane l ends every tile with the f64 sum over the tile's 64 columns of this wave of row slot (l & 15) of its lane
@@ -483,7 +516,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmv_h2s16_kernel(
   for (int64_t j0 = s0; j0 < s1; j0 += GEMM_BN) {
     f32x4 acc[4][4];
     s16_zero(acc);
-    s16_mainloop(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, r1 - j0, i0, 0, ktiles, lds);
+    s16_mainloop<CORE, false, false, B16>(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, r1 - j0, i0, 0, ktiles, lds, 0, 0, 0, half_tail != 0);
     float zs[4];
     double al[4];
 #pragma unroll
@@ -571,13 +604,14 @@ struct MmvnGammas {
   float g[8];
 };
 
-template <int NV, bool PERCOL>
+template <int NV, bool PERCOL, int CORE = S16_H2>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
     int ktiles, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
-    double* __restrict__ slab, int64_t slab_ld) {
+    double* __restrict__ slab, int64_t slab_ld, int half_tail) {
 #pragma clang fp contract(off)
+  constexpr bool B16 = CORE != S16_H2;          // plain 16-bit rows: see gauss_mmv_h2s16_kernel
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ __attribute__((aligned(16))) float xg_s[PERCOL ? NV : 1][GEMM_BM];      // row norms times (each column's) gamma log2(e)
   constexpr int64_t GR = 8;
@@ -592,7 +626,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
   if (i0 >= n || s0 >= M) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const float m2 = -2.f / (metax[0] * metaz[0]);
+  const float m2 = core_m2<CORE>(metax, metaz);
 
   if (threadIdx.x < GEMM_BM) {
     const bool in = i0 + threadIdx.x < n;
@@ -608,7 +642,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gauss_mmvn_h2s16_kernel(
   for (int64_t j0 = s0; j0 < s1; j0 += GEMM_BN) {
     f32x4 acc[4][4];
     s16_zero(acc);
-    s16_mainloop(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, ktiles, lds);     // its barriers also publish xg_s
+    s16_mainloop<CORE, false, false, B16>(acc, PX, ldpx, n, PZ + j0 * ldpz, ldpz, M - j0, i0, 0, ktiles, lds, 0, 0, 0,
+                                          half_tail != 0);     // its barriers also publish xg_s
     float zq[4];                        // column norms; without PERCOL: times gamma log2(e) already
     int64_t voff[4];                    // < 0: a column past the group / M (weight 0)
 #pragma unroll
@@ -1250,7 +1285,7 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_knm_h2w256_kernel(
   w_zero(acc);
   w_mainloop_dma<true, CORE>(acc, PX, ldpx, n, PZ, ldpz, M, i0, j0, stages, lds);      // its barriers also publish xg_s
 
-  const float m2g = -2.f / (metax[0] * metaz[0]) * gamma_log2e;    // the scales are powers of two: m2 is exact
+  const float m2g = core_m2<CORE>(metax, metaz) * gamma_log2e;     // the scales are powers of two (16-bit rows: none): m2 is exact
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 2, wc = wave & 3;
   const int cb = wc * 64 + 4 * (lane & 15);                 // first of this lane's four adjacent columns inside the tile
@@ -1935,7 +1970,7 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmv_h2w256_kernel(
   if (i0 >= n || s0 >= r1) return;       // mmv_reduce_kernel only visits the groups that exist
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 2, wc = wave & 3;
-  const float m2 = -2.f / (metax[0] * metaz[0]);
+  const float m2 = core_m2<CORE>(metax, metaz);
 
   if (threadIdx.x < W_BM) xs_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] : 0.f;
   // Lane l ends every tile with two f64 sums over the tile's 64 columns of this wave: for half h of the wave's rows,
@@ -2028,7 +2063,7 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_h2w256_kernel(
   const int64_t s0 = (int64_t)g * tg * W_BN;
   const int64_t s1 = (s0 + (int64_t)tg * W_BN < M) ? s0 + (int64_t)tg * W_BN : M;
   if (i0 >= n || s0 >= M) return;
-  const float m2 = -2.f / (metax[0] * metaz[0]);
+  const float m2 = core_m2<CORE>(metax, metaz);
   double* red = reinterpret_cast<double*>(lds);       // [NV][4 (wc)][W_BM], over the operand images (w_mainloop_dma ends on a barrier)
 
   if (threadIdx.x < W_BM) xs_s[threadIdx.x] = (i0 + threadIdx.x < n) ? xsq[i0 + threadIdx.x] : 0.f;
@@ -2307,7 +2342,8 @@ static int launch_knm_w256_t(unsigned wt, hipStream_t s, const uint32_t* PX, int
 }
 
 // `core`: CORE_H2 (operands from odx_split_f16, ld in 4-byte units >= roundup(D, 64)) or CORE_F8 (operands from
-// odx_split_f8, ld in 4-byte units >= roundup(D, 128) / 4); `stages` = 128-byte pieces per operand row.
+// odx_split_f8, ld in 4-byte units >= roundup(D, 128) / 4) or CORE_BF16 / CORE_F16 (plain 16-bit rows, ld in 4-byte units >=
+// roundup(D, 64) / 2, no meta words); `stages` = 128-byte pieces per operand row.
 static int launch_knm_w256(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
                            int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int stages, double sigma, int fmt,
                            void* K, int64_t ldk, void* Klo, int64_t ldlo, const double* w, double* wslab, int64_t wslab_ld,
@@ -2321,10 +2357,12 @@ static int launch_knm_w256(const void* PX, int64_t ldpx, const float* metax, con
   ODX_PROPAGATE(knm_rhs_fmt(w != nullptr, fmt, [&](auto rhs, auto kf) {
     constexpr bool RHS = decltype(rhs)::value;
     constexpr int FMT = decltype(kf)::value;
-    return core == CORE_F8 ? launch_knm_w256_t<RHS, FMT, CORE_F8>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages,
-                                                                  g2, K, ldk, lo, ldlo, W_KNM_GR, w, wslab, wslab_ld)
-                           : launch_knm_w256_t<RHS, FMT, CORE_H2>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages,
-                                                                  g2, K, ldk, lo, ldlo, W_KNM_GR, w, wslab, wslab_ld);
+    auto run = [&](auto c) {
+      return launch_knm_w256_t<RHS, FMT, decltype(c)::value>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages, g2, K,
+                                                             ldk, lo, ldlo, W_KNM_GR, w, wslab, wslab_ld);
+    };
+    return core == CORE_F8 ? run(IntC<CORE_F8>()) : core == CORE_BF16 ? run(IntC<CORE_BF16>()) : core == CORE_F16 ? run(IntC<CORE_F16>())
+                                                                                                                   : run(IntC<CORE_H2>());
   }));
   ODX_CHECK_LAUNCH("odx_gauss_knm_h2(w256)");
   return ODX_OK;
@@ -2830,8 +2868,22 @@ extern "C" int64_t odx_knm_bytes(int64_t n, int64_t M, int fmt) {
 }
 
 // ld (4-byte units) an operand row needs for `core`, and the 128-byte stages of a row
-static int64_t core_min_ld(int D, int core) { return core == CORE_F8 ? round_up(D, 128) / 4 : round_up(D, H2_KT); }
+static bool core_is_b16(int core) { return core == CORE_BF16 || core == CORE_F16; }
+static int64_t core_min_ld(int D, int core) {
+  if (core_is_b16(core)) return round_up(D, 64) / 2;        // 64 features per stage: D <= 64 is ONE stage (the split has two from D = 1 on)
+  return core == CORE_F8 ? round_up(D, 128) / 4 : round_up(D, H2_KT);
+}
 static int core_stages(int D, int core) { return (int)(core_min_ld(D, core) / W_KS); }
+
+// The pair of 16-bit row operands of a Gaussian entry `who` (odx_gemm_b16's contract at 64-feature granularity): 16-byte
+// aligned, row strides (elements) multiples of 64 — whole 128-byte stages — that cover D; the columns D .. stride are zero.
+static int check_b16_pair(const char* who, int D, int64_t ldx, int64_t ldz, const void* X, const void* Z) {
+  ODX_REQUIRE(ldx % 64 == 0 && ldz % 64 == 0 && ldx >= round_up(D, 64) && ldz >= round_up(D, 64) && aligned16(X) && aligned16(Z),
+              "%s: 16-bit operands must be 16-byte aligned with row strides that are multiples of 64 elements and >= roundup(D, 64) "
+              "(zero beyond D)", who);
+  ODX_REQUIRE(ldx < (1 << 25) && ldz < (1 << 25), "%s: row strides must stay below 2^25 elements (32-bit tile offsets)", who);
+  return ODX_OK;
+}
 
 static int knm_store_impl(const char* who, int core, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
                           const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma,
@@ -2844,7 +2896,7 @@ static int knm_store_impl(const char* who, int core, const void* PX, int64_t ldp
     if (ktw) ODX_CHECK_HIP(hipMemsetAsync(ktw, 0, (size_t)M * sizeof(double), as_stream(stream)));
     return ODX_OK;
   }
-  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && K && D > 0 && sigma > 0, "%s: bad argument", who);
+  ODX_REQUIRE(PX && PZ && ((metax && metaz) || core_is_b16(core)) && xsq && zsq && K && D > 0 && sigma > 0, "%s: bad argument", who);
   ODX_PROPAGATE(check_packed_pair(who, core_min_ld(D, core), ldpx, ldpz, PX, PZ));
   ODX_PROPAGATE(check_knm_block(who, fmt, M, K, ldk, Klo, ldlo));
   if (w != nullptr && (workspace == nullptr || workspace_bytes < odx_gauss_knm_h2_rhs_workspace_bytes(n, M))) {
@@ -2864,6 +2916,61 @@ extern "C" int odx_gauss_knm_h2_store(const void* PX, int64_t ldpx, const float*
                                       double* ktw, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
   return knm_store_impl("odx_gauss_knm_h2_store", CORE_H2, PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, fmt, K, ldk,
                         Klo, ldlo, w, ktw, workspace, workspace_bytes, stream);
+}
+
+// ---- rows that are 16-bit already (bf16 / f16): the Gaussian kernels at native width
+// A bf16 x bf16 product has 8 + 8 significant bits, an f16 x f16 one 11 + 11: exact in the f32 accumulator of ONE MFMA, so K
+// is f32-accurate for the rows as given with a third of the split's matrix instructions and half its operand bytes, nothing
+// packed and no f32 copy made.  The norms are the f32 sums of the exact squares, one wave per row (pad columns are zero: whole
+// 16-byte pieces are read).
+template <int CORE>
+__global__ __launch_bounds__(256) void row_sqnorm_b16_kernel(const unsigned short* __restrict__ X, int64_t ldx, int64_t n, int D,
+                                                             float* __restrict__ sq) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const unsigned short* x = X + row * ldx;
+  float acc = 0.f;
+  for (int c = lane * 8; c < D; c += 512) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(x + c);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned short lo = (unsigned short)(v[q] & 0xffffu), hi = (unsigned short)(v[q] >> 16);
+      const float a = b16_load<CORE>(&lo), b = b16_load<CORE>(&hi);
+      acc = fmaf(a, a, acc);
+      acc = fmaf(b, b, acc);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  if (lane == 0) sq[row] = acc;
+}
+
+extern "C" int odx_row_sqnorm_b16(const void* X, int64_t ldx, int64_t n, int D, int is_bf16, float* sq, odx_stream_t stream) {
+  if (n <= 0) return ODX_OK;
+  ODX_REQUIRE(X && sq && D > 0, "odx_row_sqnorm_b16: bad argument");
+  ODX_PROPAGATE(check_b16_pair("odx_row_sqnorm_b16", D, ldx, ldx, X, X));
+  ODX_REQUIRE(ceil_div(n, 4) < (1ll << 31), "odx_row_sqnorm_b16: too many rows");
+  const unsigned short* x = static_cast<const unsigned short*>(X);
+  if (is_bf16)
+    hipLaunchKernelGGL(row_sqnorm_b16_kernel<CORE_BF16>, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, as_stream(stream), x, ldx, n, D, sq);
+  else
+    hipLaunchKernelGGL(row_sqnorm_b16_kernel<CORE_F16>, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, as_stream(stream), x, ldx, n, D, sq);
+  ODX_CHECK_LAUNCH("odx_row_sqnorm_b16");
+  return ODX_OK;
+}
+
+extern "C" int64_t odx_gauss_knm_b16_store_workspace_bytes(int64_t n, int64_t M) { return odx_gauss_knm_h2_rhs_workspace_bytes(n, M); }
+
+// odx_gauss_knm_h2_store for 16-bit rows: the same wide core, tile order, epilogue (unit scales) and slab reduction; a stage is
+// 64 features, so D <= 64 runs the pipeline with a single stage.
+extern "C" int odx_gauss_knm_b16_store(const void* X, int64_t ldx, const float* xsq, int64_t n, const void* Z, int64_t ldz,
+                                       const float* zsq, int64_t M, int D, int is_bf16, double sigma, int fmt, void* K, int64_t ldk,
+                                       void* Klo, int64_t ldlo, const double* w, double* ktw, void* workspace,
+                                       int64_t workspace_bytes, odx_stream_t stream) {
+  if (n > 0 && M > 0 && D > 0) ODX_PROPAGATE(check_b16_pair("odx_gauss_knm_b16_store", D, ldx, ldz, X, Z));
+  return knm_store_impl("odx_gauss_knm_b16_store", is_bf16 ? CORE_BF16 : CORE_F16, X, ldx / 2, nullptr, xsq, n, Z, ldz / 2, nullptr, zsq, M,
+                        D, sigma, fmt, K, ldk, Klo, ldlo, w, ktw, workspace, workspace_bytes, stream);
 }
 
 // ---- S blocks, one per kernel width, from one contraction (gauss_knm_sigmas_h2w256_kernel)
@@ -3066,6 +3173,48 @@ static int launch_mmv_w256(const void* PX, int64_t ldpx, const float* metax, con
   return ODX_OK;
 }
 
+// The fused scoring with per-column centre ranges behind the entries' own operand checks: the tile core, the groups of
+// column tiles, the launch and the sum of the groups.  core: CORE_H2 (packed two-term rows with their meta words) or
+// CORE_BF16 / CORE_F16 (plain 16-bit rows, no meta); ld in 4-byte units either way.
+static int mmv_ranges_run(const char* who, int core, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                          const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D, double sigma,
+                          const double* V, int64_t ldv, const int32_t* ranges, int C, float* out, int64_t ldo, void* workspace,
+                          int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(ldo >= C && C < 65536, "%s: ldo < C or too many classes", who);
+  if (workspace == nullptr || workspace_bytes < odx_gauss_mmv_h2_workspace_bytes(n, max_range, C)) {
+    set_error("%s: workspace too small", who);
+    return ODX_ERR_WORKSPACE;
+  }
+  double* slab = static_cast<double*>(workspace);
+  const int64_t slab_ld = round_up(n, 2);
+  const int stages = core_stages(D, core);             // 128-byte pieces of an operand row; a k-tile of the 128 x 128 core is two
+  if (h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(max_range, W_BN), W_MMV_TG) * C)) {
+    auto run = [&](auto c) {
+      return launch_mmv_w256<decltype(c)::value>(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, stages, sigma, V, ldv, ranges, C,
+                                                 out, ldo, slab, slab_ld, stream);
+    };
+    return core == CORE_BF16 ? run(IntC<CORE_BF16>()) : core == CORE_F16 ? run(IntC<CORE_F16>()) : run(IntC<CORE_H2>());
+  }
+  const int tg = mmv_tg(n, max_range, C);
+  const int G = (int)mmv_groups(max_range, tg);
+  const int64_t wgs = round_up(ceil_div(n, GEMM_BM), 8) * G;
+  ODX_REQUIRE(wgs < (1ll << 31), "%s: grid too large", who);
+  auto run = [&](auto c) {
+    constexpr int CORE = decltype(c)::value;
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmv_h2s16_kernel<CORE>)));
+    hipLaunchKernelGGL(gauss_mmv_h2s16_kernel<CORE>, dim3((unsigned)wgs, (unsigned)C), dim3(GEMM_THREADS), S16_LDS_BYTES,
+                       as_stream(stream), (const uint32_t*)PX, ldpx, metax, xsq, n, (const uint32_t*)PZ, ldpz, metaz, zsq,
+                       (stages + 1) / 2, h2_gamma_log2e(sigma), V, ldv, ranges, tg, G, slab, slab_ld, stages & 1);
+    return (int)ODX_OK;
+  };
+  ODX_PROPAGATE(core == CORE_BF16 ? run(IntC<S16_BF16>()) : core == CORE_F16 ? run(IntC<S16_F16>()) : run(IntC<S16_H2>()));
+  ODX_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(mmv_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)C), dim3(256), 0, as_stream(stream), slab,
+                     slab_ld, G, tg, GEMM_BN, ranges, n, out, ldo);
+  ODX_CHECK_LAUNCH(who);
+  return ODX_OK;
+}
+
 extern "C" int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
                                 const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D,
                                 double sigma, const double* V, int64_t ldv, const int32_t* ranges, int C, float* out,
@@ -3073,31 +3222,25 @@ extern "C" int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax
   if (n <= 0 || C <= 0) return ODX_OK;
   ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && ranges && out && D > 0 && sigma > 0 && ldv >= C && max_range > 0,
               "odx_gauss_mmv_h2: bad argument");
-  const int64_t dp = round_up(D, H2_KT);
-  ODX_PROPAGATE(check_packed_pair("odx_gauss_mmv_h2", dp, ldpx, ldpz, PX, PZ));
-  ODX_REQUIRE(ldo >= C && C < 65536, "odx_gauss_mmv_h2: ldo < C or too many classes");
-  if (workspace == nullptr || workspace_bytes < odx_gauss_mmv_h2_workspace_bytes(n, max_range, C)) {
-    set_error("odx_gauss_mmv_h2: workspace too small");
-    return ODX_ERR_WORKSPACE;
-  }
-  double* slab = static_cast<double*>(workspace);
-  const int64_t slab_ld = round_up(n, 2);
-  if (h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(max_range, W_BN), W_MMV_TG) * C))
-    return launch_mmv_w256<CORE_H2>(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, (int)(dp / W_KS), sigma, V, ldv, ranges,
-                                    C, out, ldo, slab, slab_ld, stream);
-  const int tg = mmv_tg(n, max_range, C);
-  const int G = (int)mmv_groups(max_range, tg);
-  const int64_t wgs = round_up(ceil_div(n, GEMM_BM), 8) * G;
-  ODX_REQUIRE(wgs < (1ll << 31), "odx_gauss_mmv_h2: grid too large");
-  ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmv_h2s16_kernel)));
-  hipLaunchKernelGGL(gauss_mmv_h2s16_kernel, dim3((unsigned)wgs, (unsigned)C), dim3(GEMM_THREADS), S16_LDS_BYTES,
-                     as_stream(stream), (const uint32_t*)PX, ldpx, metax, xsq, n, (const uint32_t*)PZ, ldpz, metaz, zsq,
-                     (int)(dp / H2_KT), h2_gamma_log2e(sigma), V, ldv, ranges, tg, G, slab, slab_ld);
-  ODX_CHECK_LAUNCH("odx_gauss_mmv_h2");
-  hipLaunchKernelGGL(mmv_reduce_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)C), dim3(256), 0, as_stream(stream), slab,
-                     slab_ld, G, tg, GEMM_BN, ranges, n, out, ldo);
-  ODX_CHECK_LAUNCH("odx_gauss_mmv_h2(reduce)");
-  return ODX_OK;
+  ODX_PROPAGATE(check_packed_pair("odx_gauss_mmv_h2", round_up(D, H2_KT), ldpx, ldpz, PX, PZ));
+  return mmv_ranges_run("odx_gauss_mmv_h2", CORE_H2, PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, D, sigma, V, ldv, ranges, C,
+                        out, ldo, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t odx_gauss_mmv_b16_workspace_bytes(int64_t n, int64_t max_range, int T) {
+  return odx_gauss_mmv_h2_workspace_bytes(n, max_range, T);
+}
+
+// odx_gauss_mmv_h2 for 16-bit rows (both tile cores; h2_tile pins one as for the split kernels)
+extern "C" int odx_gauss_mmv_b16(const void* X, int64_t ldx, const float* xsq, int64_t n, const void* Z, int64_t ldz, const float* zsq,
+                                 int64_t max_range, int D, int is_bf16, double sigma, const double* V, int64_t ldv,
+                                 const int32_t* ranges, int C, float* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
+                                 odx_stream_t stream) {
+  if (n <= 0 || C <= 0) return ODX_OK;
+  ODX_REQUIRE(X && Z && xsq && zsq && V && ranges && out && D > 0 && sigma > 0 && ldv >= C && max_range > 0, "odx_gauss_mmv_b16: bad argument");
+  ODX_PROPAGATE(check_b16_pair("odx_gauss_mmv_b16", D, ldx, ldz, X, Z));
+  return mmv_ranges_run("odx_gauss_mmv_b16", is_bf16 ? CORE_BF16 : CORE_F16, X, ldx / 2, nullptr, xsq, n, Z, ldz / 2, nullptr, zsq, max_range,
+                        D, sigma, V, ldv, ranges, C, out, ldo, workspace, workspace_bytes, stream);
 }
 
 // ---- shared-centre scoring: all T columns of a dense V from one evaluation of K per group of up to 8 columns
@@ -3109,26 +3252,36 @@ struct MmvnArgs {
   const double* V;
   double* slab;
   int kt, T, tg, G;          // kt: k-tiles (128 x 128 core) or stages (256 x 256 core)
+  int core, half_tail;       // CORE_H2, or CORE_BF16 / CORE_F16 (plain 16-bit rows, one width); 128 x 128 core: the last k-tile is half a one
   unsigned wgs;
   hipStream_t stream;
 };
 
 // `groups` groups of NV columns from column cbase on
-template <int NV, bool WIDE, bool PERCOL>
-static int launch_mmvn_group(const MmvnArgs& a, const MmvnGammas& gm, int cbase, int groups) {
+template <int NV, bool WIDE, bool PERCOL, int CORE>
+static int launch_mmvn_group_core(const MmvnArgs& a, const MmvnGammas& gm, int cbase, int groups) {
   if (WIDE) {
-    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2w256_kernel<NV, CORE_H2, PERCOL>), W_LDS_BYTES));
-    hipLaunchKernelGGL((gauss_mmvn_h2w256_kernel<NV, CORE_H2, PERCOL>), dim3(a.wgs, (unsigned)groups), dim3(W_THREADS), W_LDS_BYTES,
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2w256_kernel<NV, CORE, PERCOL>), W_LDS_BYTES));
+    hipLaunchKernelGGL((gauss_mmvn_h2w256_kernel<NV, CORE, PERCOL>), dim3(a.wgs, (unsigned)groups), dim3(W_THREADS), W_LDS_BYTES,
                        a.stream, a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T,
                        a.tg, a.G, a.slab, a.slab_ld);
   } else {
-    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2s16_kernel<NV, PERCOL>)));
-    hipLaunchKernelGGL((gauss_mmvn_h2s16_kernel<NV, PERCOL>), dim3(a.wgs, (unsigned)groups), dim3(GEMM_THREADS), S16_LDS_BYTES,
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2s16_kernel<NV, PERCOL, CORE>)));
+    hipLaunchKernelGGL((gauss_mmvn_h2s16_kernel<NV, PERCOL, CORE>), dim3(a.wgs, (unsigned)groups), dim3(GEMM_THREADS), S16_LDS_BYTES,
                        a.stream, a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T,
-                       a.tg, a.G, a.slab, a.slab_ld);
+                       a.tg, a.G, a.slab, a.slab_ld, a.half_tail);
   }
   ODX_CHECK_LAUNCH(a.who);
   return ODX_OK;
+}
+
+template <int NV, bool WIDE, bool PERCOL>
+static int launch_mmvn_group(const MmvnArgs& a, const MmvnGammas& gm, int cbase, int groups) {
+  if constexpr (!PERCOL) {          // (a width per column exists for the split rows only: mmvn_run)
+    if (a.core == CORE_BF16) return launch_mmvn_group_core<NV, WIDE, false, CORE_BF16>(a, gm, cbase, groups);
+    if (a.core == CORE_F16) return launch_mmvn_group_core<NV, WIDE, false, CORE_F16>(a, gm, cbase, groups);
+  }
+  return launch_mmvn_group_core<NV, WIDE, PERCOL, CORE_H2>(a, gm, cbase, groups);
 }
 
 // one group of `rest` <= 8 columns on the next instantiated width
@@ -3163,10 +3316,11 @@ static int launch_mmvn(const MmvnArgs& a, double sigma, const double* sigmas) {
 static int mmvn_run(const char* who, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
                     int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma, const double* sigmas,
                     const double* V, int64_t ldv, int T, float* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
-                    odx_stream_t stream) {
-  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && out && D > 0 && ldv >= T && M > 0, "%s: bad argument", who);
-  const int64_t dp = round_up(D, H2_KT);
-  ODX_PROPAGATE(check_packed_pair(who, dp, ldpx, ldpz, PX, PZ));
+                    odx_stream_t stream, int core = CORE_H2) {
+  ODX_REQUIRE(PX && PZ && ((metax && metaz) || core_is_b16(core)) && xsq && zsq && V && out && D > 0 && ldv >= T && M > 0, "%s: bad argument", who);
+  ODX_REQUIRE(!(core_is_b16(core) && sigmas), "%s: a width per column needs the split rows", who);
+  const int stages = core_stages(D, core);            // 128-byte pieces of an operand row; a k-tile of the 128 x 128 core is two
+  ODX_PROPAGATE(check_packed_pair(who, core_min_ld(D, core), ldpx, ldpz, PX, PZ));
   ODX_REQUIRE(ldo >= T && T < 65536, "%s: ldo < T or too many columns", who);
   if (workspace == nullptr || workspace_bytes < odx_gauss_mmv_h2_workspace_bytes(n, M, T)) {
     set_error("%s: workspace too small", who);
@@ -3174,15 +3328,15 @@ static int mmvn_run(const char* who, const void* PX, int64_t ldpx, const float* 
   }
   MmvnArgs a;
   a.who = who, a.PX = (const uint32_t*)PX, a.PZ = (const uint32_t*)PZ, a.ldpx = ldpx, a.ldpz = ldpz, a.n = n, a.M = M, a.ldv = ldv;
-  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T;
+  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T, a.core = core, a.half_tail = 0;
   a.slab = static_cast<double*>(workspace), a.slab_ld = round_up(n, 2), a.stream = as_stream(stream);
   const bool wide = h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
   int64_t wgs;
   if (wide) {
-    a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = (int)(dp / W_KS);
+    a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = stages;
     wgs = round_up(ceil_div(n, W_BM), 8) * a.G;
   } else {
-    a.tg = mmv_tg(n, M, T), a.G = (int)mmv_groups(M, a.tg), a.kt = (int)(dp / H2_KT);
+    a.tg = mmv_tg(n, M, T), a.G = (int)mmv_groups(M, a.tg), a.kt = (stages + 1) / 2, a.half_tail = stages & 1;
     wgs = round_up(ceil_div(n, GEMM_BM), 8) * a.G;
   }
   ODX_REQUIRE(wgs < (1ll << 31), "%s: grid too large", who);
@@ -3206,6 +3360,19 @@ extern "C" int odx_gauss_mmvn_h2(const void* PX, int64_t ldpx, const float* meta
   ODX_REQUIRE(sigma > 0, "odx_gauss_mmvn_h2: bad argument");
   return mmvn_run("odx_gauss_mmvn_h2", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, nullptr, V, ldv, T, out, ldo,
                   workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t odx_gauss_mmvn_b16_workspace_bytes(int64_t n, int64_t M, int T) { return odx_gauss_mmv_h2_workspace_bytes(n, M, T); }
+
+// odx_gauss_mmvn_h2 for 16-bit rows (both tile cores)
+extern "C" int odx_gauss_mmvn_b16(const void* X, int64_t ldx, const float* xsq, int64_t n, const void* Z, int64_t ldz, const float* zsq,
+                                  int64_t M, int D, int is_bf16, double sigma, const double* V, int64_t ldv, int T, float* out,
+                                  int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  if (n <= 0 || T <= 0) return ODX_OK;
+  ODX_REQUIRE(sigma > 0 && D > 0, "odx_gauss_mmvn_b16: bad argument");
+  ODX_PROPAGATE(check_b16_pair("odx_gauss_mmvn_b16", D, ldx, ldz, X, Z));
+  return mmvn_run("odx_gauss_mmvn_b16", X, ldx / 2, nullptr, xsq, n, Z, ldz / 2, nullptr, zsq, M, D, sigma, nullptr, V, ldv, T, out, ldo,
+                  workspace, workspace_bytes, stream, is_bf16 ? CORE_BF16 : CORE_F16);
 }
 
 extern "C" int64_t odx_gauss_mmvn_h2_sigmas_workspace_bytes(int64_t n, int64_t M, int T) {

@@ -23,10 +23,34 @@ from . import hip
 from .knm_path import PathOps, _p
 
 
+B16_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def rows16_operand(X, device=None):
+    """X (n, D) bf16 / f16 as the 16-bit kernels' operand (include/odx.h, "rows that are 16-bit already"): the (n, D) view of
+    a row-major block whose base is 16-byte aligned, whose row stride is a multiple of 64 elements (one 128-byte stage) and
+    whose columns D .. stride are zero.  A tensor that already is one — rows back to back, D a multiple of 64, aligned — is
+    returned as it is (a stride beyond D cannot be adopted: what lies between the rows is not known to be zero); every other
+    one is copied into a zeroed block of roundup(D, 64) columns."""
+    if X.dtype not in B16_DTYPES or X.dim() != 2:
+        raise ValueError("rows16_operand: expected a 2-D bf16 / f16 tensor, got %s of shape %s" % (X.dtype, tuple(X.shape)))
+    if device is not None:
+        X = X.to(device)
+    n, D = X.shape
+    if D % 64 == 0 and (n == 0 or (X.stride(1) == 1 and X.stride(0) == D and X.data_ptr() % 16 == 0)):
+        return X
+    buf = torch.zeros((n, (D + 63) // 64 * 64), dtype=X.dtype, device=X.device)
+    buf[:, :D] = X
+    return buf[:, :D]
+
+
 class Features:
     """Row-major f32 rows (n x D, leading dimension a multiple of 4) plus their squared norms and, once a
-    Gaussian-kernel call has needed it, the packed two-term f16 split of the rows (P, meta: odx_split_f16)."""
-    __slots__ = ("X", "sq", "n", "D", "ld", "P", "meta", "own_pack", "P8", "meta8", "sq8", "zero_row", "cmap")
+    Gaussian-kernel call has needed it, the packed two-term f16 split of the rows (P, meta: odx_split_f16).
+    Under HipBackend.native16 the rows of a bf16 / f16 tensor stay as they are: X is then the 16-bit operand itself
+    (rows16_operand), sq its f32 norms, and there is no P / meta, ever; `f32` caches the exact f32 form that every call
+    without a 16-bit kernel goes through (HipBackend.f32)."""
+    __slots__ = ("X", "sq", "n", "D", "ld", "P", "meta", "own_pack", "P8", "meta8", "sq8", "zero_row", "cmap", "f32", "f32_made")
 
     def __init__(self, X, sq, D, P=None, meta=None):
         self.X, self.sq, self.n, self.D, self.ld = X, sq, X.shape[0], D, X.stride(0) if X.shape[0] else X.shape[1]
@@ -35,6 +59,13 @@ class Features:
         self.own_pack = P is None       # False: P was gathered from another matrix's split and carries ITS scale
         self.P8 = self.meta8 = self.sq8 = None     # e4m3 packing (odx_split_f8), made on demand by the throughput-only fp8 kernels
         self.cmap = None                # centres that repeat: their odx.cols.ColumnMap (knm_rhs then stores the distinct columns only)
+        self.f32 = None
+        self.f32_made = None            # (X._version, stream, event) of the moment `f32` was queued: HipBackend.f32
+
+    @property
+    def b16(self):
+        """The rows are a 16-bit operand (native16), not f32."""
+        return self.X.dtype in B16_DTYPES
 
 
 class Rows16:
@@ -131,6 +162,12 @@ class HipBackend(PathOps):
     # its stores, not its contraction, while D is small, and there the shared contraction saves nothing: measured slower
     # than the single builds at D = 256 and 0.65 of their time at D = 1024, four widths (profiles/sigma_grid.md).
     sigma_grid_min_features = 1024
+    # True: features() of a bf16 / f16 tensor keeps the 16-bit rows as the operand, and the Gaussian build on the wide tile
+    # core and the fused scoring run on them directly (odx_gauss_knm_b16_store / odx_gauss_mmv_b16 / odx_gauss_mmvn_b16: one
+    # exact MFMA term per product, nothing packed, no f32 copy); every other call takes the exact f32 form (f32()).  An
+    # attribute like shared_mmv_min, not an option.  False: 16-bit tensors are converted to f32 on entry, as ever.
+    # Whether it becomes the default is a matter of the measurements in profiles/b16_features.md.
+    native16 = False
 
     def __init__(self, device=None):
         self.lib = hip.require_gpu()
@@ -226,6 +263,8 @@ class HipBackend(PathOps):
         16-byte aligned (copied only when the caller's tensor is not already so)."""
         if not torch.is_tensor(X):
             X = torch.as_tensor(X)
+        if self.native16 and X.dtype in B16_DTYPES and X.dim() == 2 and X.shape[1] > 0:
+            return self._features16(X, norms)
         X = X.to(device=self.device, dtype=torch.float32)
         if X.dim() != 2:
             raise ValueError("features: expected a 2-D (n, D) tensor, got shape %s" % (tuple(X.shape),))
@@ -250,6 +289,60 @@ class HipBackend(PathOps):
         if n:
             hip.check(self.lib.odx_row_sqnorm_f32(_p(X), X.stride(0), n, D, _p(sq), self._stream()), "odx_row_sqnorm_f32")
         return Features(X, sq, D)
+
+    def _features16(self, X, norms):
+        """features() of a bf16 / f16 tensor under native16: the rows stay 16-bit (copied only when they do not meet the
+        operand contract already), the norms are the f32 sums of their exact squares; nothing is packed."""
+        X = rows16_operand(X, self.device)
+        n, D = X.shape
+        sq = None
+        if norms:
+            sq = torch.empty(n, dtype=torch.float32, device=self.device)
+            if n:
+                hip.check(self.lib.odx_row_sqnorm_b16(_p(X), X.stride(0), n, D, 1 if X.dtype == torch.bfloat16 else 0, _p(sq),
+                                                      self._stream()), "odx_row_sqnorm_b16")
+        return Features(X, sq, D)
+
+    def f32(self, F):
+        """The f32 form of a Features: F itself unless its rows are 16-bit; then their exact upcast with its own norms (and,
+        on demand, packing), made once and kept on F.  What every call without a 16-bit kernel works on."""
+        if not getattr(F, "b16", False):
+            return F
+        cur = torch.cuda.current_stream(self.device)
+        made = F.f32_made
+        if F.f32 is None or made[0] != F.X._version:          # (rows rewritten in place since: the f32 form is made again)
+            F.f32 = self.features(F.X.float(), norms=F.sq is not None)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            F.f32_made = (F.X._version, cur, ev)
+        elif made[1] != cur:
+            # made on another stream (a preconditioner chain's side stream, say) than the one that reads it now: this stream
+            # waits for the upcast and the norms, and the allocator is told of the second user
+            cur.wait_event(made[2])
+            for t in (F.f32.X, F.f32.sq, F.f32.P, F.f32.meta):
+                if t is not None:
+                    t.record_stream(cur)
+        F.f32.cmap = F.cmap
+        return F.f32
+
+    def with_norms(self, F):
+        """F with its squared norms: F itself when it has them.  Rows adopted without norms (features(X, norms=False)) get them
+        now — 16-bit rows in place, from the operand that exists (no second copy of a padded block); f32 rows through
+        features(), as ever."""
+        if F.sq is not None:
+            return F
+        if not F.b16:
+            return self.features(F.X)
+        F.sq = torch.empty(F.n, dtype=torch.float32, device=self.device)
+        if F.n:
+            hip.check(self.lib.odx_row_sqnorm_b16(_p(F.X), F.ld, F.n, F.D, 1 if F.X.dtype == torch.bfloat16 else 0, _p(F.sq),
+                                                  self._stream()), "odx_row_sqnorm_b16")
+        return F
+
+    def _native16_pair(self, F, Zf):
+        """Both operands are 16-bit rows of one type and the Gaussian kernels are the matrix-core ones: the 16-bit entries
+        serve the pair.  Every other mix goes through f32()."""
+        return getattr(F, "b16", False) and getattr(Zf, "b16", False) and F.X.dtype == Zf.X.dtype and self.gauss == "h2"
 
     def masked_stream(self, cus, complement=False):
         """A stream confined to `cus` compute units, spread evenly over the XCDs (logical CU i sits on XCC i % 8, so the
@@ -315,6 +408,10 @@ class HipBackend(PathOps):
     def rows(self, F, idx):
         """MyCenterSelector.select: gather rows (their norms, and their packed split if it exists) by index."""
         idx = torch.as_tensor(idx, dtype=torch.int64, device=self.device).reshape(-1)
+        if F.b16:           # 16-bit rows: the gathered rows are an operand again (stride a multiple of 64, zero pad columns)
+            buf = torch.zeros((idx.numel(), (F.D + 63) // 64 * 64), dtype=F.X.dtype, device=self.device)
+            buf[:, :F.D] = F.X.index_select(0, idx)
+            return Features(buf[:, :F.D], F.sq.index_select(0, idx), F.D)
         ld = (F.D + 3) // 4 * 4
         buf = torch.zeros((idx.numel(), ld), dtype=torch.float32, device=self.device)
         buf[:, :F.D] = F.X.index_select(0, idx)
@@ -325,7 +422,8 @@ class HipBackend(PathOps):
         return Z
 
     def pack8(self, F):
-        """Make sure F carries its e4m3 packing (odx_split_f8); returns F."""
+        """Make sure F carries its e4m3 packing (odx_split_f8); returns F (16-bit rows: their f32 form)."""
+        F = self.f32(F)
         if F.P8 is None:
             ldp8 = (F.D + 127) // 128 * 128
             F.P8 = torch.empty((F.n, ldp8), dtype=torch.uint8, device=self.device)
@@ -337,7 +435,9 @@ class HipBackend(PathOps):
 
     def pack(self, F, zero_row=False):
         """Make sure F carries its packed f16 split (odx_split_f16); returns F.  zero_row: the packed rows are followed by
-        one all-zero row in memory (what gemm_h2_taps reads for a position outside the map)."""
+        one all-zero row in memory (what gemm_h2_taps reads for a position outside the map).  16-bit rows are never packed:
+        their f32 form is, and is returned."""
+        F = self.f32(F)
         if F.P is not None and zero_row and not F.zero_row:
             # a packing that exists but lacks the trailing zero row (advisor, round 5: it was silently handed on and the tap
             # gather read past its end): packed again with the row when the split is this matrix's own, refused otherwise
@@ -366,6 +466,7 @@ class HipBackend(PathOps):
     def precond(self, Zf, sigma, lam, eps, out=None, ws_key="precond"):
         """`out`: optional preallocated (4, M, ld) f64 tensor (e.g. owned by another stream); `ws_key` names the
         scratch buffer, so that factorisations in flight on different streams do not share one."""
+        Zf = self.f32(Zf)                    # (M x D is small: the chain takes the centres' f32 form)
         M, D = Zf.n, Zf.D
         ld = (M + 1) // 2 * 2
         P = Precond()
@@ -391,6 +492,7 @@ class HipBackend(PathOps):
         t_stop > 0: T's inverse stays partial, its merge levels of t_stop rows and more are not run
         (odx_falkon_precond_batched_partial_f64); a class with more than t_stop centres then carries its block boundaries in
         Precond.blocks, and its LTi / LTit are for trmv alone."""
+        Zfs = [self.f32(z) for z in Zfs]
         B = len(Zfs)
         if not 1 <= B <= self.MAX_CLASS_BATCH:
             raise ValueError("precond_batched: 1..%d classes per call, got %d" % (self.MAX_CLASS_BATCH, B))
@@ -493,6 +595,9 @@ class HipBackend(PathOps):
             raise ValueError("knm: knm_storage 'stream' stores no K_nM block (knm_rhs hands out a streamed shard)")
         if fmt != "f32" or self.gauss == "f8":
             return self._knm_store(F, Zf, sigma, fmt, None, out, None)[0]
+        if self._native16_pair(F, Zf) and n > 0 and self.lib.odx_gauss_h2_tile(n, M) == 256 and not self.direct_small(n, M, F.D):
+            return self._knm_store(F, Zf, sigma, "f32", None, out, None)[0]       # the wide core's f32 build, on the 16-bit rows
+        F, Zf = self.f32(F), self.f32(Zf)
         K = self._knm_block(n, M, "f32", out)
         ld = K.ld
         if self.direct_small(n, M, F.D):
@@ -526,13 +631,23 @@ class HipBackend(PathOps):
         n, M = F.n, Zf.n
         K = self._knm_block(n, M, fmt, out)
         f8 = self.gauss == "f8"
-        (self.pack8(F), self.pack8(Zf)) if f8 else (self.pack(F), self.pack(Zf))
+        native = self._native16_pair(F, Zf)
+        if not native:
+            F, Zf = self.f32(F), self.f32(Zf)
+            (self.pack8(F), self.pack8(Zf)) if f8 else (self.pack(F), self.pack(Zf))
         ws = None
         if w is not None:
             w = w.to(dtype=torch.float64, device=self.device).contiguous()
             if rhs_out is None:
                 rhs_out = torch.empty(M, dtype=torch.float64, device=self.device)
-            ws = self._workspace("knm_rhs", self.lib.odx_gauss_knm_h2_rhs_workspace_bytes(n, M))
+            ws = self._workspace("knm_rhs", (self.lib.odx_gauss_knm_b16_store_workspace_bytes if native else
+                                             self.lib.odx_gauss_knm_h2_rhs_workspace_bytes)(n, M))
+        if native:          # 16-bit rows of one type: the same build on them as they are (nothing packed, no meta)
+            hip.check(self.lib.odx_gauss_knm_b16_store(_p(F.X), F.ld, _p(F.sq), n, _p(Zf.X), Zf.ld, _p(Zf.sq), M, F.D,
+                                                       1 if F.X.dtype == torch.bfloat16 else 0, float(sigma), hip.KNM_CODE[fmt], _p(K.K),
+                                                       K.ld, _p(K.lo), K.ld, _p(w), _p(rhs_out if w is not None else None), _p(ws),
+                                                       ws.numel() if ws is not None else 0, self._stream()), "odx_gauss_knm_b16_store")
+            return K, rhs_out
         fn, PX, mx, PZ, mz = ((self.lib.odx_gauss_knm_f8_store, F.P8, F.meta8, Zf.P8, Zf.meta8) if f8 else
                               (self.lib.odx_gauss_knm_h2_store, F.P, F.meta, Zf.P, Zf.meta))
         sqx, sqz = (F.sq8, Zf.sq8) if f8 else (F.sq, Zf.sq)
@@ -549,6 +664,8 @@ class HipBackend(PathOps):
         if rhs_out is None:
             rhs_out = torch.empty(M, dtype=torch.float64, device=self.device)
         fmt = self.knm_format(n, M)
+        if not self._native16_pair(F, Zf) or fmt == "stream":
+            F, Zf = self.f32(F), self.f32(Zf)
         if fmt == "stream":
             # no block: a handle from which every pass recomputes K; b0 = K' w is one streamed pass (v = 0)
             self.pack(F), self.pack(Zf)
@@ -564,7 +681,8 @@ class HipBackend(PathOps):
         if cmap is not None and fmt in ("u24", "bf16") and n > 0:
             # centres that repeat: the block of the DISTINCT centres (the same build kernel over the same operand rows, picked
             # from the full list's packing: its columns are the full block's), K' w expanded to the list's M positions
-            self.pack8(Zf) if self.gauss == "f8" else self.pack(Zf)
+            if not getattr(Zf, "b16", False):
+                self.pack8(Zf) if self.gauss == "f8" else self.pack(Zf)
             first, col_of = cmap.on(self.device)[:2]
             K, b_d = self._knm_store(F, self.rows(Zf, first), sigma, fmt, w, out, None)
             K.cmap, K.Mv = cmap, M
@@ -597,6 +715,7 @@ class HipBackend(PathOps):
         itself); in every other situation (streamed shards, column-mapped centres, small or direct blocks, the f32 / f8
         cores, few features) knm_rhs is looped.  outs: one preallocated buffer (or None) per width.  All blocks of a call
         are resident together."""
+        F, Zf = self.f32(F), self.f32(Zf)             # (the grouped build exists for the split rows only)
         sigmas = [float(s) for s in sigmas]
         outs = [None] * len(sigmas) if outs is None else list(outs)
         if len(outs) != len(sigmas):
@@ -617,6 +736,7 @@ class HipBackend(PathOps):
     def _knm_store_sigmas(self, F, Zf, sigmas, fmt, w, outs):
         """The blocks of 1 .. ODX_GRID_MAX_SIGMAS widths in storage format `fmt` from one contraction on the wide tile core
         (odx_gauss_knm_h2_store_sigmas), with the fused right-hand sides when w is given: [(K_s, K_s' w)]."""
+        F, Zf = self.f32(F), self.f32(Zf)
         n, M, S = F.n, Zf.n, len(sigmas)
         self.pack(F), self.pack(Zf)
         if w is not None:
@@ -783,15 +903,25 @@ class HipBackend(PathOps):
         Mtot, T = V.shape
         if Mtot != Zf.n:
             raise ValueError("mmv: V has %d rows but there are %d centres" % (Mtot, Zf.n))
+        native = self._native16_pair(F, Zf)          # 16-bit rows of one type: scored as they are; every other mix in f32
+        if not native:
+            F, Zf = self.f32(F), self.f32(Zf)
+        is_bf16 = 1 if F.X.dtype == torch.bfloat16 else 0
         shared = ranges is None and self.gauss == "h2" and self.shared_mmv_min is not None and T >= self.shared_mmv_min
         if shared and F.n > 0 and T > 0 and Mtot > 0:
             # all columns weigh all centres: one evaluation of K per group of up to 8 columns (the per-column launch's bits)
             if out is None:
                 out = torch.empty((F.n, T), dtype=torch.float32, device=self.device)
-            self.pack(F), self.pack(Zf)
             if Vs.stride(1) == 1 and Vs.stride(0) >= T:
                 V = Vs
-            ws = self._workspace("mmv", self.lib.odx_gauss_mmvn_h2_workspace_bytes(F.n, Mtot, T))
+            ws = self._workspace("mmv", (self.lib.odx_gauss_mmvn_b16_workspace_bytes if native else
+                                         self.lib.odx_gauss_mmvn_h2_workspace_bytes)(F.n, Mtot, T))
+            if native:
+                hip.check(self.lib.odx_gauss_mmvn_b16(_p(F.X), F.ld, _p(F.sq), F.n, _p(Zf.X), Zf.ld, _p(Zf.sq), Mtot, F.D, is_bf16,
+                                                      float(sigma), _p(V), V.stride(0), T, _p(out), out.stride(0), _p(ws), ws.numel(),
+                                                      self._stream()), "odx_gauss_mmvn_b16")
+                return out
+            self.pack(F), self.pack(Zf)
             hip.check(self.lib.odx_gauss_mmvn_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), F.n, _p(Zf.P), Zf.P.stride(0),
                                                  _p(Zf.meta), _p(Zf.sq), Mtot, F.D, float(sigma), _p(V), V.stride(0), T,
                                                  _p(out), out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_mmvn_h2")
@@ -815,6 +945,12 @@ class HipBackend(PathOps):
             hip.check(self.lib.odx_gauss_mmv_f8(_p(F.P8), F.P8.stride(0), _p(F.meta8), _p(F.sq8), F.n, _p(Zf.P8), Zf.P8.stride(0),
                                                 _p(Zf.meta8), _p(Zf.sq8), mr, F.D, float(sigma), _p(V), V.stride(0), _p(ranges), T,
                                                 _p(out), out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_mmv_f8")
+        elif native:
+            mr = Mtot if max_range is None else max(1, min(int(max_range), Mtot))
+            ws = self._workspace("mmv", self.lib.odx_gauss_mmv_b16_workspace_bytes(F.n, mr, T))
+            hip.check(self.lib.odx_gauss_mmv_b16(_p(F.X), F.ld, _p(F.sq), F.n, _p(Zf.X), Zf.ld, _p(Zf.sq), mr, F.D, is_bf16, float(sigma),
+                                                 _p(V), V.stride(0), _p(ranges), T, _p(out), out.stride(0), _p(ws), ws.numel(),
+                                                 self._stream()), "odx_gauss_mmv_b16")
         elif self.gauss == "h2":
             self.pack(F), self.pack(Zf)
             mr = Mtot if max_range is None else max(1, min(int(max_range), Mtot))
@@ -834,6 +970,7 @@ class HipBackend(PathOps):
         (odx_gauss_mmvn_h2_sigmas, on the tile core the dispatch rule picks for T columns): column c is bit for bit column c
         of mmv(F, Zf, sigmas[c], V) on the shared route.  Otherwise mmv is looped over the distinct widths and their columns
         copied."""
+        F, Zf = self.f32(F), self.f32(Zf)             # (a width per column exists for the split rows only)
         V = V.to(device=self.device, dtype=torch.float64)
         if V.dim() == 1:
             V = V[:, None]
@@ -870,6 +1007,7 @@ class HipBackend(PathOps):
     # ------------------------------------------------------------------ RLS (A7)
     def rls_gram(self, F, idx, Yt, G, XtY):
         """G (D1 x D1 lower) += [X 1]'[X 1],  XtY (4 x D1) += Yt [X 1]  over rows ``idx`` of F."""
+        F = self.f32(F)
         nc = idx.numel()
         if nc == 0:
             return
@@ -892,15 +1030,18 @@ class HipBackend(PathOps):
 
     def rls_rows_form(self, F):
         """Whether the Grams of F's rows can be formed on their own (rls_gram_begin): see odx_rls_rows_form."""
+        F = self.f32(F)
         return bool(F.n) and bool(self.lib.odx_rls_rows_form(_p(F.X), F.ld, F.D))
 
     def rls_gram_zeros(self, F, C):
+        F = self.f32(F)
         D1 = F.D + 1
         return torch.zeros((C, D1, (D1 + 1) // 2 * 2), dtype=torch.float64, device=self.device)
 
     def rls_gram_begin(self, F, idx_pad, seg_off, seg_len, G):
         """Queue the Grams of the classes alone (they need the rows, not the targets) into G = rls_gram_zeros(F, C), which
         rls_train_batched(begun=G) completes.  Needs rls_rows_form(F)."""
+        F = self.f32(F)
         C, D = len(seg_len), F.D
         npad = int(idx_pad.numel())
         if not npad:
@@ -933,6 +1074,7 @@ class HipBackend(PathOps):
         """rls_gram_begin that also forms the RAW targets' products in the same sweep (odx_rls_gram_raw_batched_f64): Yraw (n, 4)
         f32 by row id -> O5 (C, 5, ld) f64 = [Y 1]' X, which rls_train_batched(raw=(O5, stats, cnt)) turns into the whitened
         targets' X' Yw once the statistics exist — no second sweep over the rows behind the Grams."""
+        F = self.f32(F)
         C, D = len(seg_len), F.D
         D1 = D + 1
         ld = (D1 + 1) // 2 * 2
@@ -951,6 +1093,7 @@ class HipBackend(PathOps):
         block of rls_gram_begin for the same rows, queued on stream `after`: only Yt [X 1] is formed here (beside the Grams —
         it writes other entries of G than they do), and the solves wait for `after`.  Returns W (C, 4, ldw) f64 and info
         (C,) int32."""
+        F = self.f32(F)
         C, D = len(seg_len), F.D
         D1 = D + 1
         ld = (D1 + 1) // 2 * 2
@@ -985,6 +1128,7 @@ class HipBackend(PathOps):
         return W, info
 
     def rls_predict_rows(self, F, idx, W, out=None):
+        F = self.f32(F)
         nc = F.n if idx is None else idx.numel()
         Pm = torch.empty((nc, 4), dtype=torch.float64, device=self.device) if out is None else out
         if tuple(Pm.shape) != (nc, 4) or Pm.dtype != torch.float64 or not Pm.is_contiguous():
@@ -998,6 +1142,7 @@ class HipBackend(PathOps):
     def rls_predict_rows_batched(self, F, idx_all, starts, W, out):
         """out (total, 4) f64 = [X 1] w for the rows of len(starts) <= 32 classes with one launch: idx_all holds the row ids
         class after class, class c's first at starts[c]; W (C, 4, ldw)."""
+        F = self.f32(F)
         total = int(idx_all.numel())
         C = len(starts)
         if total == 0:
@@ -1010,6 +1155,7 @@ class HipBackend(PathOps):
     # ------------------------------------------------------------------ dense f32 product (RLS apply)
     def gemm_nt(self, Fa, Fb):
         """(n, m) f32 = Fa.X (n, D) @ Fb.X (m, D)' on the f32 MFMA core (exact f32 fmaf chain)."""
+        Fa, Fb = self.f32(Fa), self.f32(Fb)
         out = torch.empty((Fa.n, Fb.n), dtype=torch.float32, device=self.device)
         if Fa.n and Fb.n:
             hip.check(self.lib.odx_gemm_nt_f32(_p(Fa.X), Fa.ld, _p(Fb.X), Fb.ld, _p(out), Fb.n, Fa.n, Fb.n, Fa.D,

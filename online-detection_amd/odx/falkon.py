@@ -238,9 +238,11 @@ class _FalkonBase:
         if c is not None and c[0] is ny and c[1] == ny._version and c[2] is be:
             if ny.is_cuda:          # possibly made on another stream than the one that scores with them now
                 cur = torch.cuda.current_stream()
-                for t in (c[3].X, c[3].sq, getattr(c[3], "P", None), getattr(c[3], "meta", None)):
-                    if t is not None:
-                        t.record_stream(cur)
+                z32 = getattr(c[3], "f32", None)          # 16-bit centres: the f32 form the fallbacks read, if it exists
+                for z in (c[3], z32):
+                    for t in (() if z is None else (z.X, z.sq, getattr(z, "P", None), getattr(z, "meta", None))):
+                        if t is not None:
+                            t.record_stream(cur)
             return c[3]
         Zf = be.features(ny)
         if torch.is_tensor(ny):
@@ -354,6 +356,9 @@ def fit_batch(estimators, Xs, Ys, streams=None):
             sel = est.center_selection.select(F.X, None)
             Zf = be.features(sel[0] if isinstance(sel, tuple) else sel)
         est.M = Zf.n
+        if hasattr(be, "f32"):
+            be.f32(Zf)          # 16-bit centres: their f32 form (the chains' operand) is made HERE, on the caller's stream, which
+            #                     the chains' side streams and the builds' class streams all wait for
         y = torch.as_tensor(Y).reshape(F.n, -1)
         if y.shape[1] != 1:
             raise ValueError("odx FALKON fits one right-hand side per model; got Y with %d columns" % y.shape[1])
@@ -361,7 +366,7 @@ def fit_batch(estimators, Xs, Ys, streams=None):
 
     def finish(i):
         if getattr(Fs[i], "sq", 0) is None:
-            Fs[i] = be.features(Fs[i].X)
+            Fs[i] = be.with_norms(Fs[i]) if hasattr(be, "with_norms") else be.features(Fs[i].X)
         if yvs[i].dim() == 2:
             yvs[i] = be.vec(yvs[i][:, 0])
     # classes that share (sigma, penalty, jitter) share a chain; the reference's classes always do
@@ -527,6 +532,8 @@ class BatchFit:
             sel = est.center_selection.select(F.X, None)
             Zf = be.features(sel[0] if isinstance(sel, tuple) else sel)
             est.M = Zf.n
+            if hasattr(be, "f32"):
+                be.f32(Zf)      # (as in fit_batch: the centres' f32 form on the caller's stream, before the chain is queued)
             y = torch.as_tensor(Y).reshape(F.n, -1)
             if y.shape[1] != 1:
                 raise ValueError("odx FALKON fits one right-hand side per model; got Y with %d columns" % y.shape[1])
@@ -579,7 +586,7 @@ class BatchFit:
                 cur.wait_stream(side)
             return fit_batch(self.est, self.Xs, self.Ys, streams=self.streams)
         for i in range(n_cls):                # behind the chains: row norms of the training sets, label uploads
-            Fs[i] = be.features(Fs[i].X)
+            Fs[i] = be.with_norms(Fs[i]) if hasattr(be, "with_norms") else be.features(Fs[i].X)
         yvs = [be.vec(y[:, 0]) for y in self.ys]
         Mmax = int(self.block.shape[2])
         b0s = torch.zeros((n_cls, (Mmax + 1) // 2 * 2), dtype=torch.float64, device=be.device)

@@ -69,7 +69,10 @@ class _OnlineHead:
             return torch.full((n, C), fill, dtype=torch.float32, device=F.X.device)
         if self._cls_cache is None:
             dev = F.X.device
-            ny = torch.cat([m.ny_points_.to(dev, torch.float32) for m in live])
+            # 16-bit features against models whose centres are all of that same 16-bit type: the centres stay 16-bit and the
+            # batched scoring runs on the rows as they are (HipBackend.native16); every other mix is scored in f32
+            dt = F.X.dtype if getattr(F, "b16", False) and all(m.ny_points_.dtype == F.X.dtype for m in live) else torch.float32
+            ny = torch.cat([m.ny_points_.to(dev, dt) for m in live])
             total = ny.shape[0]
             V = torch.zeros((total, C), dtype=torch.float64, device=dev)
             ranges = torch.zeros((C, 2), dtype=torch.int32)

@@ -68,6 +68,16 @@ SIGNATURES = {
     "odx_gauss_mmvn_h2_sigmas_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "odx_gauss_mmvn_h2_sigmas": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i64,
                                         _vp, _i64, _vp]),
+    "odx_row_sqnorm_b16": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "odx_gauss_knm_b16_store_workspace_bytes": (_i64, [_i64, _i64]),
+    "odx_gauss_knm_b16_store": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _f64, _i32, _vp, _i64, _vp, _i64, _vp, _vp,
+                                       _vp, _i64, _vp]),
+    "odx_gauss_mmv_b16_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "odx_gauss_mmv_b16": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _f64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64,
+                                 _vp]),
+    "odx_gauss_mmvn_b16_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "odx_gauss_mmvn_b16": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _f64, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
+                                  _vp]),
     "odx_gauss_knm_h2_store_sigmas_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "odx_gauss_knm_h2_store_sigmas": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp,
                                              _i64, _vp, _vp, _i64, _vp, _i64, _vp]),

@@ -390,6 +390,7 @@ class PathOps:
         lambda) and own their LAi / LAit; member l equals precond(Zf, sigma, lams[l], eps) bit for bit.  `out`: optional
         (2 + 2 L, M, ld) f64 tensor.  A member's info is its word of one (L,) tensor."""
         from .backend import Precond
+        Zf = self.f32(Zf)                    # (16-bit centres: the chain takes their f32 form, as precond does)
         lams = [float(x) for x in lams]
         L, M, D = len(lams), Zf.n, Zf.D
         if not 1 <= L <= self.MAX_CLASS_BATCH:
