@@ -347,6 +347,22 @@ int64_t odx_knm_fwd_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv
 int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
                        const double* V, int64_t ldv, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
                        odx_stream_t stream);
+/* The row-weighted form of odx_knm_fwd_bwdn_q: out[q] = K' (D[wrow[q]] o (K V[q])), q = 0 .. nv - 1, 1 <= nv <= 8, from ONE read
+ * of a compact-format block (what the fold fits of a cross-validation share: a fit on the rows outside a fold is the full fit
+ * with row weights, odx.solver.falkon_fit_cv).  V / out as odx_knm_fwd_bwdn_q.  D: G >= 1 f64 rows of n row weights, ldd doubles
+ * apart (even, >= n); wrow: a HOST array of nv int32, read during the call and carried to the kernel by value — the row of D
+ * that vector q uses, -1 = no weights (D may be NULL when every entry is -1).  T_out: NULL, or nv f64 rows of n, ldt >= n
+ * doubles apart: T_out[q][r] = (K V[q])[r] BEFORE the weight.  Weights past n and T_out[q][n:] are never touched; a weight of
+ * exactly 0 removes its row.  The widths of odx_knm_fwd_bwdn_q (8 vectors up to M = 2524, 4 up to M = 5084), nv = 1 and 2 on
+ * the 4-wide kernel with zero vectors behind them; the workspace twin returns a negative value for any other (M, fmt, nv)
+ * and the call ODX_ERR_UNSUPPORTED.  The row dots of a block end as one value per lane: that lane loads its row's weight
+ * and multiplies once, so `out` with every wrow[q] = -1 is bit for bit odx_knm_fwd_bwdn_q's (nv >= 3), and the same bits
+ * with or without T_out.  Slab per workgroup and vector, fixed-order reduction: bitwise reproducible, no atomics. */
+int64_t odx_knm_fwd_bwdn_q_rw_workspace_bytes(int64_t n, int64_t M, int fmt, int nv);
+int odx_knm_fwd_bwdn_q_rw(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
+                          const double* V, int64_t ldv, const double* D, int64_t ldd, const int32_t* wrow, double* out,
+                          int64_t ldo, double* T_out, int64_t ldt, void* workspace, int64_t workspace_bytes,
+                          odx_stream_t stream);
 /* out[q] = K' W[q], q = 0 .. nv - 1, 1 <= nv <= 8, from ONE read of a compact-format block: the right-hand sides K' (Y / n) of a
  * multi-output fit (odx.solver.falkon_fit_multi), which odx_knm_fwd_bwd_q(v = NULL, w = W[q]) gives one read of the block at a
  * time.  W: nv f64 rows of n weights, ldw doubles apart; out: nv f64 rows of M, ldo apart; rows 16-byte aligned, ldw and ldo

@@ -33,6 +33,12 @@
 // a reduction in which every thread reads all partials from LDS, as the narrower kernels do, spilled at NV R = 32.)
 // R is as large as the budget allows without scratch: the bytes a CU keeps in flight are NT x CH x R chunks.
 // (tools/kernel_resources.py lists registers and scratch of every instantiation; profiles/falkon_path.md quotes it.)
+//
+// The row-weighted form  out[q] = K' (d_q o (K v[q]))  (odx_knm_fwd_bwdn_q_rw, 1 <= nv <= 8: the states of a K-fold
+// cross-validation, solver.falkon_fit_cv, each a fit with row weights) is the same kernel template with one more parameter (NvRows).  Between
+// the phases a row dot is ONE value in one lane (`s` of lane q R + r): that lane loads the row's weight ahead of phase 1,
+// multiplies once, and wave 0 stores the unweighted value to T_out — no per-thread weights, nothing further held in
+// vector registers across a phase (profiles/cross_validation.md quotes the registers of both forms).
 #include <algorithm>
 #include <stdlib.h>
 
@@ -41,11 +47,28 @@
 
 namespace odx {
 
-template <int NT, int CH, int R, int NV, int FMT>
+// The row weights and row products of the weighted form (odx_knm_fwd_bwdn_q_rw), carried by value: vector q multiplies its
+// row dots with row w[q] of D (-1: with nothing) before phase 2, and T (when given) receives them as they were before.
+struct NvRows {
+  const double* D;
+  int64_t ldd;
+  int w[8];
+  double* T;
+  int64_t ldt;
+};
+
+__device__ __forceinline__ const NvRows& nv_rows(const NvRows& rw) { return rw; }
+
+// ROWS: nothing (the unweighted kernel: neither its parameters nor its code depend on the weighted form), or one NvRows (the
+// weighted form: every statement of it sits under `if constexpr (RW)`).  A pack and not a shared body under two kernels:
+// the unweighted kernels' code generation stays what profiles/falkon_path.md measured.
+template <int NT, int CH, int R, int NV, int FMT, typename... ROWS>
 __global__ __launch_bounds__(NT, 2) void knm_passnv_kernel(const unsigned short* __restrict__ Khi, int64_t ldk,
                                                            const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                            int64_t M, int nv, const double* __restrict__ V, int64_t ldv,
-                                                           double* __restrict__ slab, int64_t slab_ld) {
+                                                           double* __restrict__ slab, int64_t slab_ld, ROWS... rows) {
+  constexpr bool RW = sizeof...(ROWS) != 0;
+  static_assert(sizeof...(ROWS) <= 1, "at most one NvRows");
   constexpr int NW = NT / 64;
   constexpr int CW = QCW;
   extern __shared__ __attribute__((aligned(16))) double vsq[];       // [NV][vcap]
@@ -104,6 +127,23 @@ __global__ __launch_bounds__(NT, 2) void knm_passnv_kernel(const unsigned short*
   __syncthreads();  // vsq is complete
   int pp = 0;
   for (; blk < nblk; blk += nwg) {
+    // (weighted form) lane q R + r is the one that ends phase 1 with row dot r of vector q in `s` below: it loads that
+    // row's weight here, ahead of phase 1, which covers the latency; the other lanes, vectors without a weight row and
+    // rows past n keep 1.0 and load nothing
+    double wgt = 1.0;
+    if constexpr (RW) {
+      const NvRows& rw = nv_rows(rows...);
+      // (an opaque lane index: the address is formed here, block by block, not kept in registers for the whole loop)
+      int ln;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+      if (ln < NV * R) {
+        int wr = -1;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) wr = ln / R == q ? rw.w[q] : wr;
+        const int64_t row = blk * R + ln % R;
+        if (wr >= 0 && row < n) wgt = rw.D[(int64_t)wr * rw.ldd + row];
+      }
+    }
     double t[NV][R];
 #pragma unroll
     for (int q = 0; q < NV; ++q)
@@ -171,6 +211,13 @@ __global__ __launch_bounds__(NT, 2) void knm_passnv_kernel(const unsigned short*
       const int vi = lane < NV * R ? lane : 0;
 #pragma unroll
       for (int u = 0; u < NW; ++u) s += red[pp][u][vi];
+      if constexpr (RW) {
+        // the row product K v as it is (wave 0 stores it: every wave holds the same totals), then the weight, once
+        const NvRows& rw = nv_rows(rows...);
+        const int64_t row = blk * R + lane % R;
+        if (rw.T != nullptr && wave == 0 && lane < NV * R && lane / R < nv && row < n) rw.T[(int64_t)(lane / R) * rw.ldt + row] = s;
+        s *= wgt;
+      }
       const int slo = __double2loint(s), shi = __double2hiint(s);
 #pragma unroll
       for (int q = 0; q < NV; ++q)
@@ -230,6 +277,12 @@ __global__ __launch_bounds__(NT, 2) void knm_passnv_kernel(const unsigned short*
   }
 }
 
+// the two kernels' types (the template's pack of trailing parameters is closed by the conversion)
+using NvKernel = void (*)(const unsigned short*, int64_t, const unsigned char*, int64_t, int64_t, int64_t, int, const double*, int64_t,
+                          double*, int64_t);
+using NvRowsKernel = void (*)(const unsigned short*, int64_t, const unsigned char*, int64_t, int64_t, int64_t, int, const double*,
+                              int64_t, double*, int64_t, NvRows);
+
 struct NvCfg {
   int nt, ch, r, nvt, wg_per_cu;      // nvt: the instantiated width (4 or 8) that serves the call's nv
 };
@@ -238,11 +291,13 @@ static int64_t nv_lds_bytes(const NvCfg& c, int64_t chunks) {
   return (int64_t)c.nvt * (chunks + 1) * 4 * 8;      // dynamic part; the static red[2][NT / 64][nvt * r] comes on top
 }
 
-// the configuration of an nv-vector pass over M columns, or false: the vectors (and the reduction scratch) do not fit in LDS
-static bool pick_nvcfg(int64_t M, int nv, NvCfg* cfg) {
-  if (M <= 0 || nv < 3 || nv > 8) return false;
+// the configuration of an nv-vector pass over M columns, or false: the vectors (and the reduction scratch) do not fit in LDS.
+// nv_min: the narrowest call the entry takes — 3 for the unweighted entry (pairs and singles have kernels of their own in
+// knm_pass_q.hip), 1 for the weighted one (nv = 1 and 2 run on the 4-wide instantiation, as nv = 3 does)
+static bool pick_nvcfg(int64_t M, int nv, NvCfg* cfg, int nv_min = 3) {
+  if (M <= 0 || nv < nv_min || nv > 8) return false;
   const int64_t chunks = (M + 3) / 4;
-  const int nvt = q_nvt(nv);
+  const int nvt = nv <= 4 ? 4 : 8;
   NvCfg c;
   if (nvt == 8) {
     if (chunks <= 256) c = {256, 1, 4, 8, 2};
@@ -268,10 +323,17 @@ static int nvgrid_for(const NvCfg& cfg, int64_t n, int cus) {
   return (int)(g < 1 ? 1 : g);
 }
 
-// launch(kernel, threads) for the instantiation cfg names: exactly the configurations pick_nvcfg hands out
-template <int FMT, typename Launch>
+// launch(kernel, threads) for the instantiation cfg names (RW: of the weighted kernel): exactly the configurations
+// pick_nvcfg hands out
+template <int FMT, bool RW, typename Launch>
 static int dispatch_passnv(const NvCfg& cfg, Launch&& launch) {
-#define ODX_NV(NT_, CH_, R_, NV_) return launch(knm_passnv_kernel<NT_, CH_, R_, NV_, FMT>, NT_)
+#define ODX_NV(NT_, CH_, R_, NV_)                                                                        \
+  do {                                                                                                   \
+    if constexpr (RW)                                                                                    \
+      return launch(static_cast<NvRowsKernel>(knm_passnv_kernel<NT_, CH_, R_, NV_, FMT, NvRows>), NT_);    \
+    else                                                                                                 \
+      return launch(static_cast<NvKernel>(knm_passnv_kernel<NT_, CH_, R_, NV_, FMT>), NT_);                \
+  } while (0)
   if (cfg.nvt == 8) {
     if (cfg.nt == 256) ODX_NV(256, 1, 4, 8);
     if (cfg.ch == 1) ODX_NV(512, 1, 4, 8);
@@ -284,44 +346,83 @@ static int dispatch_passnv(const NvCfg& cfg, Launch&& launch) {
 #undef ODX_NV
 }
 
-}  // namespace odx
-
-using namespace odx;
-
-extern "C" int64_t odx_knm_fwd_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv) {
+static int64_t passnv_workspace_bytes(int64_t n, int64_t M, int fmt, int nv, int nv_min) {
   NvCfg cfg;
-  if (!q_format(fmt) || !pick_nvcfg(M, nv, &cfg)) return ODX_ERR_UNSUPPORTED;
+  if (!q_format(fmt) || !pick_nvcfg(M, nv, &cfg, nv_min)) return ODX_ERR_UNSUPPORTED;
   if (n <= 0) return 0;
   return (int64_t)nv * workspace_cus() * cfg.wg_per_cu * round_up(M, 4) * (int64_t)sizeof(double);
 }
 
-extern "C" int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
-                                  const double* V, int64_t ldv, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
-                                  odx_stream_t stream) {
-  ODX_REQUIRE(M > 0 && nv >= 3 && nv <= 8, "odx_knm_fwd_bwdn_q: M <= 0 or nv outside 3 .. 8");
+// The two entries' host code.  rw: the weights and row products of the weighted entry (its caller has checked them), or
+// nullptr — the unweighted entry, which launches the unweighted kernels.
+static int passnv_run(const char* who, int nv_min, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n,
+                      int64_t M, int nv, const double* V, int64_t ldv, double* out, int64_t ldo, const NvRows* rw, void* workspace,
+                      int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(M > 0 && nv >= nv_min && nv <= 8, "%s: M <= 0 or nv outside %d .. 8", who, nv_min);
   ODX_REQUIRE(V && out && aligned16(V) && aligned16(out) && ldv % 2 == 0 && ldo % 2 == 0 && ldv >= M && ldo >= M,
-              "odx_knm_fwd_bwdn_q: V and out must be 16-byte aligned with even ldv, ldo >= M");
+              "%s: V and out must be 16-byte aligned with even ldv, ldo >= M", who);
   hipStream_t s = as_stream(stream);
   if (n <= 0) {
     ODX_CHECK_HIP(hipMemset2DAsync(out, (size_t)ldo * sizeof(double), 0, (size_t)M * sizeof(double), (size_t)nv, s));
     return ODX_OK;
   }
-  ODX_PROPAGATE(check_q_block("odx_knm_fwd_bwdn_q", K, ldk, Klo, ldlo, fmt, M));
+  ODX_PROPAGATE(check_q_block(who, K, ldk, Klo, ldlo, fmt, M));
   NvCfg cfg;
-  if (!pick_nvcfg(M, nv, &cfg)) {
-    set_error("odx_knm_fwd_bwdn_q: %d vectors of M = %lld do not fit in LDS (use narrower groups)", nv, (long long)M);
+  if (!pick_nvcfg(M, nv, &cfg, nv_min)) {
+    set_error("%s: %d vectors of M = %lld do not fit in LDS (use narrower groups)", who, nv, (long long)M);
     return ODX_ERR_UNSUPPORTED;
   }
   const int grid = nvgrid_for(cfg, n, pass_cus());
   const int64_t slab_ld = round_up(M, 4);
-  ODX_PROPAGATE(require_workspace("odx_knm_fwd_bwdn_q", workspace, workspace_bytes, (int64_t)nv * grid * slab_ld * (int64_t)sizeof(double)));
+  ODX_PROPAGATE(require_workspace(who, workspace, workspace_bytes, (int64_t)nv * grid * slab_ld * (int64_t)sizeof(double)));
   double* slab = static_cast<double*>(workspace);
   const size_t lds = (size_t)nv_lds_bytes(cfg, (M + 3) / 4);
   ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
-    return dispatch_passnv<decltype(f)::value>(cfg, [&](auto* kernel, int threads) {
+    constexpr int FMT = decltype(f)::value;
+    if (rw != nullptr)
+      return dispatch_passnv<FMT, true>(cfg, [&](auto* kernel, int threads) {
+        return q_launch(kernel, dim3(grid), threads, lds, s, b.hi, b.ldk, b.lo, b.ldlo, b.n, b.M, nv, V, ldv, slab, slab_ld, *rw);
+      });
+    return dispatch_passnv<FMT, false>(cfg, [&](auto* kernel, int threads) {
       return q_launch(kernel, dim3(grid), threads, lds, s, b.hi, b.ldk, b.lo, b.ldlo, b.n, b.M, nv, V, ldv, slab, slab_ld);
     });
   }));
-  ODX_CHECK_LAUNCH("odx_knm_fwd_bwdn_q");
+  ODX_CHECK_LAUNCH(who);
   return reduce_nv(nv, M, grid, slab, slab_ld, out, ldo, s);
+}
+
+}  // namespace odx
+
+using namespace odx;
+
+extern "C" int64_t odx_knm_fwd_bwdn_q_workspace_bytes(int64_t n, int64_t M, int fmt, int nv) {
+  return passnv_workspace_bytes(n, M, fmt, nv, 3);
+}
+
+extern "C" int odx_knm_fwd_bwdn_q(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
+                                  const double* V, int64_t ldv, double* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
+                                  odx_stream_t stream) {
+  return passnv_run("odx_knm_fwd_bwdn_q", 3, K, ldk, Klo, ldlo, fmt, n, M, nv, V, ldv, out, ldo, nullptr, workspace, workspace_bytes,
+                    stream);
+}
+
+extern "C" int64_t odx_knm_fwd_bwdn_q_rw_workspace_bytes(int64_t n, int64_t M, int fmt, int nv) {
+  return passnv_workspace_bytes(n, M, fmt, nv, 1);
+}
+
+extern "C" int odx_knm_fwd_bwdn_q_rw(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M, int nv,
+                                     const double* V, int64_t ldv, const double* D, int64_t ldd, const int32_t* wrow, double* out,
+                                     int64_t ldo, double* T_out, int64_t ldt, void* workspace, int64_t workspace_bytes,
+                                     odx_stream_t stream) {
+  const char* who = "odx_knm_fwd_bwdn_q_rw";
+  ODX_REQUIRE(nv >= 1 && nv <= 8 && wrow != nullptr, "%s: nv outside 1 .. 8, or no wrow", who);
+  NvRows rw = {D, ldd, {-1, -1, -1, -1, -1, -1, -1, -1}, T_out, ldt};
+  bool weighted = false;
+  for (int q = 0; q < nv; ++q) {
+    rw.w[q] = wrow[q] < 0 ? -1 : (int)wrow[q];
+    weighted = weighted || rw.w[q] >= 0;
+  }
+  ODX_REQUIRE(!weighted || (D != nullptr && ldd % 2 == 0 && ldd >= n), "%s: D must be rows of n weights, an even ldd >= n apart", who);
+  ODX_REQUIRE(T_out == nullptr || ldt >= n, "%s: T_out must be rows of n doubles, ldt >= n apart", who);
+  return passnv_run(who, 1, K, ldk, Klo, ldlo, fmt, n, M, nv, V, ldv, out, ldo, &rw, workspace, workspace_bytes, stream);
 }

@@ -20,7 +20,7 @@ import torch
 
 from . import backend as _backend
 from . import options as _options
-from .solver import SolverOptions, falkon_fit, falkon_fit_grid, falkon_fit_multi, falkon_fit_path
+from .solver import SolverOptions, cv_folds, falkon_fit, falkon_fit_cv, falkon_fit_grid, falkon_fit_multi, falkon_fit_path
 
 
 class FalkonOptions:
@@ -71,6 +71,16 @@ class GaussianKernel:
 
     def __repr__(self):
         return "GaussianKernel(sigma=%g)" % self.sigma
+
+
+class CVResult:
+    """What `fit_cv` returns.  estimators: one per penalty, fitted on ALL rows and sharing `ny_points_` (predict_path accepts
+    them); empty without refit.  scores: (n, L) f32, column l the scores of every row by the model of penalty l that never
+    saw the row's fold.  fold_of: (n,) the fold assignment used.  fold_alphas: (L, folds, M) f64, the fold fits.
+    mse: (L,) f64, the mean over the rows of (scores - Y)^2."""
+
+    def __init__(self, estimators, scores, fold_of, fold_alphas, mse):
+        self.estimators, self.scores, self.fold_of, self.fold_alphas, self.mse = estimators, scores, fold_of, fold_alphas, mse
 
 
 def block_ranges(v):
@@ -183,6 +193,54 @@ class _FalkonBase:
                 est._centres(Zf)
             out.append(est)
         return out
+
+    def fit_cv(self, X, Y, penalties, folds=5, fold_of=None, seed=0, refit=True):
+        """A `folds`-fold cross-validation of `penalties` from ONE K_nM block (solver.falkon_fit_cv): the held-out score of
+        every row at every penalty and, with refit, one estimator per penalty fitted on all rows — a CVResult.  The centres
+        are selected once, from all rows, as in fit_path, and every fold fit uses them.  fold_of: the caller's (n,)
+        assignment with values in [0, folds); None: cv_folds(n, folds, seed), which leaves the global RNG alone.  This
+        estimator is the template and stays as it is."""
+        import copy
+        be = _backend.get_backend()
+        F = be.features(X)
+        if isinstance(self.center_selection, str):
+            Zf = be.rows(F, torch.randperm(F.n)[: self.M])
+        else:
+            sel = self.center_selection.select(F.X, None)
+            Zf = be.features(sel[0] if isinstance(sel, tuple) else sel)
+        y = torch.as_tensor(Y).reshape(F.n, -1)
+        if y.shape[1] != 1:
+            raise ValueError("odx FALKON fits one right-hand side per model (the reference trains one "
+                             "binary classifier per fit); got Y with %d columns" % y.shape[1])
+        penalties, folds = [float(p) for p in penalties], int(folds)
+        if fold_of is None:
+            fold_of = cv_folds(F.n, folds, seed)
+        yv = be.vec(y[:, 0])
+        alphas, heldout = falkon_fit_cv(be, F, yv, Zf, self.kernel.sigma, penalties, fold_of, folds, int(self.maxiter),
+                                        self.options.solver_options(), refit=refit)
+        if hasattr(be, "release_helper_streams"):
+            be.release_helper_streams()
+        host = self._cpu_model and not (torch.is_tensor(X) and X.is_cuda)
+        scores = heldout.t().to(torch.float32).contiguous()
+        mse = ((scores.double() - yv[:, None]) ** 2).mean(0)
+        fold_alphas = alphas[:, :folds].clone()
+        if host:
+            scores, mse, fold_alphas = scores.cpu(), mse.cpu(), fold_alphas.cpu()
+        ny = Zf.X.contiguous() if Zf.X.stride(0) != Zf.D else Zf.X
+        if self._cpu_model:
+            ny = ny.cpu()                    # once: the members share ONE tensor (predict_path asks for that)
+        out = []
+        for l, pen in enumerate(penalties if refit else []):
+            est = copy.copy(self)
+            est.__dict__.pop("_zf", None)
+            est.penalty, est.M = pen, Zf.n
+            est.alpha_, est.ny_points_ = alphas[l, folds].clone().reshape(-1, 1), ny
+            if est._cpu_model:
+                est.alpha_ = est.alpha_.cpu()
+            else:
+                est._centres(Zf)
+            out.append(est)
+        return CVResult(out, scores, torch.as_tensor(fold_of), fold_alphas, mse)
 
     def fit_grid(self, X, Y, sigmas, penalties):
         """One fitted estimator of this class per (sigma, penalty): S lists of L estimators, from one contraction of X Z' per

@@ -116,6 +116,9 @@ SIGNATURES = {
     "odx_knm_fwd_bwd2_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_knm_fwd_bwdn_q_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "odx_knm_fwd_bwdn_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "odx_knm_fwd_bwdn_q_rw_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "odx_knm_fwd_bwdn_q_rw": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64,
+                                     _vp, _i64, _vp]),
     "odx_knm_bwdn_q_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "odx_knm_bwdn_q": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "odx_knm_fwdn_q_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),

@@ -314,6 +314,81 @@ class PathOps:
                     self.ktk(K, v=V[j, :M], out=out[j, :M])
         return out
 
+    # ------------------------------------------------------------------ several vectors with row weights
+    def _ktkn_rows_plan(self, K, L):
+        """The calls ktkn_rows makes for L vectors over a stored block, in order: (kind, first vector, count) with kind "nv"
+        (odx_knm_fwd_bwdn_q_rw: one read), "wide" (odx_knm_fwdn_q + odx_knm_bwdn_q: two reads) or "single" (two ktk per
+        vector: two reads each)."""
+        if not _compact(K):
+            return [("single", l, 1) for l in range(L)]
+        code = hip.KNM_CODE[K.fmt]
+        if self.lib.odx_knm_fwd_bwdn_q_rw_workspace_bytes(max(K.n, 1), K.M, code, 1) >= 0:
+            return [("nv", l, g) for l, g in _groups(L, self.ktkn_width(K))]
+        return [("wide", l, g) for l, g in _groups(L, self.WIDE_PASS_MAX)]
+
+    def ktkn_rows_reads(self, K, L):
+        """The number of reads of the block ktkn_rows(K, V, ...) makes for L vectors."""
+        return sum({"nv": 1, "wide": 2, "single": 2 * g}[kind] for kind, _, g in self._ktkn_rows_plan(K, L))
+
+    def ktkn_rows(self, K, V, Dw, wrow, out=None, t_out=None):
+        """out[l] = K' (Dw[wrow[l]] o (K V[l])) for the L >= 1 rows of V ((L, >= M) f64): the pass of CG states that are fits
+        with row weights over one block (solver.falkon_fit_cv: the folds of a cross-validation).  Dw: (G, >= n) f64, a row
+        of n row weights each; wrow: L ints, the row of Dw vector l uses, -1 = no weights.  t_out: optional (L, >= n) f64
+        that receives the row products K V[l] as they are BEFORE the weight; `out` is the same bits with or without it.
+        A compact block within the NV pass's widths: groups of ktkn_width(K) rows, groups of 1 and 2 included, from ONE read
+        each (odx_knm_fwd_bwdn_q_rw).  A wider compact block (up to M = 20440): groups of up to 8 from TWO reads each,
+        whatever wide_pass_min says (T = K V by odx_knm_fwdn_q, T o Dw, then odx_knm_bwdn_q).  f32 blocks (small, not
+        HBM-bound): per vector ktk(K, v, t_out=t), then ktk(K, w=d o t).  ktkn_rows_reads(K, L) counts the reads.  Rows of V,
+        out and Dw must be 16-byte aligned on compact blocks, and those of t_out on the wide route.  A streamed shard
+        (its rows pass in chunks) and a block with a column map: ValueError."""
+        if K.fmt == "stream":
+            raise ValueError("ktkn_rows: needs a stored K_nM block (a streamed shard's rows pass in chunks)")
+        _no_map("ktkn_rows", K)
+        L, M, n = V.shape[0], K.M, K.n
+        wrow = [int(w) for w in wrow]
+        G = Dw.shape[0] if Dw is not None else 0
+        if len(wrow) != L or any(not -1 <= w < G for w in wrow):
+            raise ValueError("ktkn_rows: wrow must name, for each of the %d vectors, one of the %d rows of Dw or -1, got %r" % (L, G, wrow))
+        if out is None:
+            out = torch.zeros((L, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
+        _check_matrix("ktkn_rows", "V", V, L, M)
+        _check_matrix("ktkn_rows", "out", out, L, M)
+        if G:
+            _check_matrix("ktkn_rows", "Dw", Dw, G, n)
+        if t_out is not None:
+            _check_matrix("ktkn_rows", "t_out", t_out, L, n)
+        for kind, l, g in self._ktkn_rows_plan(K, L):
+            if kind == "single":
+                t = t_out[l, :n] if t_out is not None else self._workspace("ktkn_t", max(n, 1) * 8)[:n * 8].view(torch.float64)
+                self.ktk(K, v=V[l, :M], out=out[l, :M], t_out=t)
+                w = t if wrow[l] < 0 else t * Dw[wrow[l], :n]
+                self.ktk(K, w=w, out=out[l, :M])
+                continue
+            _check_aligned("ktkn_rows", V=V, out=out, **({"Dw": Dw} if G else {}))
+            if kind == "nv":
+                nbytes = self._pass_bytes("odx_knm_fwd_bwdn_q_rw", max(n, 1), M, hip.KNM_CODE[K.fmt], g)
+                ws = self._workspace("ktk", nbytes)
+                self._call("odx_knm_fwd_bwdn_q_rw", *_qblock(K), n, M, g, _p(V[l]), V.stride(0), _p(Dw if G else None),
+                           Dw.stride(0) if G else 0, (ctypes.c_int32 * g)(*wrow[l:l + g]), _p(out[l]), out.stride(0),
+                           _p(None if t_out is None else t_out[l]), 0 if t_out is None else t_out.stride(0), _p(ws), ws.numel())
+                continue
+            # two reads: T = K V (it is t_out), W = T o Dw in the "ktkn_t" workspace, out = K' W
+            ldt = (max(n, 1) + 1) // 2 * 2
+            W = self._workspace("ktkn_t", g * ldt * 8)[:g * ldt * 8].view(torch.float64).view(g, ldt)
+            if t_out is not None:
+                _check_aligned("ktkn_rows", t_out=t_out)
+                T = t_out[l:l + g]
+            else:
+                T = W
+            self.kvn(K, V[l:l + g], out=T)
+            for j in range(g):
+                if wrow[l + j] >= 0:
+                    torch.mul(T[j, :n], Dw[wrow[l + j], :n], out=W[j, :n])
+                elif T is not W:
+                    W[j, :n].copy_(T[j, :n])
+            self._nv_call("odx_knm_bwdn_q", "ktk", K, g, W, out[l:])
+        return out
+
     def ktwn(self, K, W, out=None):
         """out[t] = K' W[t] for the T >= 1 rows of W ((T, >= K.n) f64): the right-hand sides of T label columns.  A compact
         stored block: groups of up to 8 rows from ONE read each (odx_knm_bwdn_q, every M the compact passes serve); a group

@@ -459,10 +459,14 @@ def falkon_fit_grid(be, F, y, Zf, sigmas, lams, maxiter=20, opt=None, n_total=No
     return alphas
 
 
-def _fit_members(be, K, members, M, n, maxiter, opt, ar, ph, B0=None):
+def _fit_members(be, K, members, M, n, maxiter, opt, ar, ph, B0=None, weights=None):
     """The L conjugate-gradient states (P, lam, b0) of `members` over ONE block K in lock step: the driver falkon_fit_path (one
     P per lambda, one b0) and falkon_fit_multi (one P and lambda, one b0 per label column: B0, the (L, Mp) matrix the b0 are
-    rows of) share.  Returns the alphas, (L, M) f64."""
+    rows of) share.  Returns the alphas, (L, M) f64.
+
+    weights (with B0; falkon_fit_cv): (Dw, wrow, tk, scores) — the states are fits with ROW WEIGHTS, state l with row wrow[l]
+    of Dw (-1: none), so the exchange is one be.ktkn_rows; tk / scores: None, or the (L, >= n) matrices whose rows receive
+    each state's row products K v and accumulate its K alpha (scores_from_cg)."""
     L = len(members)
     Mp = (M + 1) // 2 * 2                                # rows of the shared matrices stay 16-byte aligned
     # the fold of the periodic full residual (see falkon_fit_path): streamed shards whose one build serves 2 L vectors
@@ -475,6 +479,12 @@ def _fit_members(be, K, members, M, n, maxiter, opt, ar, ph, B0=None):
     def exchange(k, rows):
         """One ktkn over the k L rows in play, the partials summed."""
         TTr, CCr = TT[:k * L], CC[:k * L]
+        if weights is not None:
+            # (stored blocks only: no fold, k = 1.  The full-residual exchange asks for no rows, so a state's tk is never
+            # overwritten by K x)
+            with ph("ktkn_rows"):
+                be.ktkn_rows(K, TTr, weights[0], weights[1], out=CCr, t_out=weights[2] if rows else None)
+            return
         with ph("ktkn"):
             if hasattr(be, "ktkn"):
                 be.ktkn(K, TTr, out=CCr)
@@ -500,6 +510,8 @@ def _fit_members(be, K, members, M, n, maxiter, opt, ar, ph, B0=None):
             c = _CG(P=P, lam=lam, B=sh.B[l, :M], X=sh.X[l, :M], R=sh.R[l, :M], Pv=sh.Pv[l, :M], AP=sh.AP[l, :M],
                     AX=sh.AX[l, :M] if can_fold else None, state=be.zeros(4),
                     v=(sh.v[0][l, :M], sh.v[1][l, :M] if can_fold else None), io=_slots(TT, CC, M, L, l))
+            if weights is not None and weights[3] is not None:
+                c.tk, c.scores = weights[2][l, :K.n], weights[3][l, :K.n]
             be.cg_init(c.B, c.X, c.R, c.Pv, c.state)
             cgs.append(c)
     else:
@@ -560,6 +572,108 @@ def falkon_fit_multi(be, F, Y, Zf, sigma, lam, maxiter=20, opt=None, n_total=Non
                     be.ktk(K, w=Wn[t, :nl], out=B0[t + 1, :M])
         _sum(ar, B0[1:])
     return _fit_members(be, K, [(P, float(lam), B0[t, :M]) for t in range(T)], M, n, maxiter, opt, ar, ph, B0=B0)
+
+
+def cv_folds(n, folds, seed=0):
+    """A balanced random assignment of n rows to `folds` folds: an (n,) int64 host tensor with values in [0, folds), fold
+    sizes differing by one at most, drawn from a torch.Generator of its own seeded with `seed` (the global RNG is not
+    touched)."""
+    n, folds = int(n), int(folds)
+    if folds < 2 or n < folds:
+        raise ValueError("cv_folds: needs 2 <= folds <= n, got folds = %d, n = %d" % (folds, n))
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    fold_of = torch.empty(n, dtype=torch.int64)
+    fold_of[torch.randperm(n, generator=g)] = torch.arange(n, dtype=torch.int64) % folds
+    return fold_of
+
+
+def falkon_fit_cv(be, F, y, Zf, sigma, lams, fold_of, folds, maxiter=20, opt=None, refit=True, phase=None, knm_out=None,
+                  knm_blocks=None):
+    """A `folds`-fold cross-validation of the penalties `lams` from ONE K_nM block: per penalty the fits on the rows outside
+    each fold, the score of every row by the fit that never saw its fold, and (refit) the fit on all rows.
+
+    The preconditioner depends on the centres, sigma and lambda only, never on the rows, and a fit on the rows outside fold
+    f is the full fit with the row weights d_f[i] = (n / n_f) [fold_of[i] != f] (n_f rows outside the fold):
+    K' diag(d_f) K / n = K_f' K_f / n_f, right-hand side K' (d_f o y) / n.  So the fold fits and the fit on all rows are
+    folds + 1 conjugate-gradient states over one block that share one preconditioner — what falkon_fit_multi drives, with
+    the row-weighted pass in the exchange: one be.knm_rhs (its fused right-hand side serves the all-rows state), one
+    be.precond_path for all penalties, the weight rows once, the fold states' right-hand sides from one be.ktwn, and per
+    penalty one lock-step run whose every iteration is one be.ktkn_rows (phase "ktkn_rows") and one be.trmvn per
+    triangular product.  Row i is held out of state fold_of[i], and K alpha = sum_i a_i (K v_i) (scores_from_cg): the
+    direction exchange hands out the row products, every state accumulates them, and the held-out scores are gathered —
+    no scoring pass.  Where scores_from_cg(be, K) does not hold (bf16 blocks) they come from one dense be.mmv over the
+    stacked fold alphas.  No host synchronisation inside the loops.
+
+    fold_of: (n,) integer tensor (device or host), values in [0, folds).  One stored shard: no row shards, and a streamed
+    shard is refused (ValueError), as are folds < 2, an empty fold, a fold of all rows and bad `lams`.
+    Returns (alphas, heldout): alphas (L, folds + refit, M) f64, the last member the fit on all rows when refit;
+    heldout (L, n) f64."""
+    opt = opt or SolverOptions()
+    lams = [float(x) for x in lams]
+    if not lams or any(not (math.isfinite(x) and x > 0.0) for x in lams):
+        raise ValueError("falkon_fit_cv: lams must be a non-empty sequence of finite positive penalties, got %r" % (lams,))
+    folds = int(folds)
+    if folds < 2:
+        raise ValueError("falkon_fit_cv: needs at least 2 folds, got %d" % folds)
+    if not hasattr(be, "ktkn_rows"):
+        raise NotImplementedError("falkon_fit_cv: the backend %r has no row-weighted pass (ktkn_rows); there is no slower route"
+                                  % getattr(be, "name", be))
+    nl = F.n
+    fo = torch.as_tensor(fold_of)
+    if fo.dim() != 1 or fo.numel() != nl or fo.dtype.is_floating_point or fo.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError("falkon_fit_cv: fold_of must be an integer tensor of the %d rows of F, got %s %r" % (nl, fo.dtype, tuple(fo.shape)))
+    fo_host = fo.to(device="cpu", dtype=torch.int64)
+    if nl == 0 or int(fo_host.min()) < 0 or int(fo_host.max()) >= folds:
+        raise ValueError("falkon_fit_cv: fold_of must hold values in [0, %d)" % folds)
+    counts = torch.bincount(fo_host, minlength=folds)
+    if bool((counts == nl).any()):
+        raise ValueError("falkon_fit_cv: a fold holds all rows (nothing to fit on)")
+    if bool((counts == 0).any()):
+        raise ValueError("falkon_fit_cv: fold %d has no rows" % int((counts == 0).nonzero()[0]))
+    L, S = len(lams), folds + bool(refit)
+    n = float(nl)
+    M = Zf.n
+    Mp, ldn = (M + 1) // 2 * 2, (nl + 1) // 2 * 2      # (rows 16-byte aligned for odd M and n too)
+    ph = phase if phase is not None else (lambda name: _NoPhase())
+
+    with ph("knm"):
+        K, b0 = be.knm_rhs(F, Zf, sigma, y * (1.0 / n), out=knm_out)
+    if getattr(K, "fmt", None) == "stream":
+        raise ValueError("falkon_fit_cv: needs a stored K_nM block (a streamed shard's rows pass in chunks: no row weights)")
+    if knm_blocks is not None:
+        knm_blocks.append(K)
+    with ph("precond"):
+        Ps = be.precond_path(Zf, sigma, lams, opt.pc_epsilon)
+    # the weight rows d_f, and the right-hand sides K' (d_f o y) / n of the fold states
+    fo_dev = fo_host.to(be.device)
+    scale = be.vec([n / float(nl - int(c)) for c in counts])
+    Dw = be.zeros(folds * ldn).view(folds, ldn)
+    Dw[:, :nl] = (fo_dev[None, :] != torch.arange(folds, device=fo_dev.device)[:, None]).to(torch.float64) * scale[:, None]
+    Wn = be.zeros(folds * ldn).view(folds, ldn)
+    Wn[:, :nl] = Dw[:, :nl] * (y * (1.0 / n))[None, :]
+    B0 = be.zeros(S * Mp).view(S, Mp)                    # rows 0 .. folds - 1: the fold states; the last: all rows
+    with ph("ktwn"):
+        be.ktwn(K, Wn, out=B0[:folds])
+    if refit:
+        B0[folds, :M].copy_(b0)
+    wrow = list(range(folds)) + [-1] * (S - folds)
+    acc = scores_from_cg(be, K)
+    alphas = be.zeros(L * S * M).view(L, S, M)
+    heldout = be.zeros(L * nl).view(L, nl)
+    for l, (P, lam) in enumerate(zip(Ps, lams)):
+        tk = be.zeros(S * ldn).view(S, ldn) if acc else None
+        scores = be.zeros(S * ldn).view(S, ldn) if acc else None
+        alphas[l].copy_(_fit_members(be, K, [(P, lam, B0[s, :M]) for s in range(S)], M, n, maxiter, opt, lambda v: v, ph, B0=B0,
+                                     weights=(Dw, wrow, tk, scores)))
+        if acc:
+            heldout[l].copy_(scores[:folds, :nl].gather(0, fo_dev[None, :])[0])       # row i from the state that never saw it
+    if not acc:
+        V = alphas[:, :folds].reshape(L * folds, M).t().contiguous()
+        sc = be.mmv(F, Zf, sigma, V)
+        for l in range(L):
+            heldout[l].copy_(sc[:, l * folds:(l + 1) * folds].gather(1, fo_dev[:, None].to(sc.device))[:, 0])
+    return alphas, heldout
 
 
 def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_total=None, shard=None, knm_outs=None,
