@@ -196,6 +196,34 @@ int odx_gauss_mmvn_h2_sigmas(const void* PX, int64_t ldpx, const float* metax, c
                              const double* sigmas, const double* V, int64_t ldv, int T,
                              float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
+/* ---- Radial kernels from the Gaussian tiles' contraction.  With d^2 = max(0, |x|^2 + |z|^2 - 2 x.z) and u = sqrt(2 nu d^2) / sigma:
+ *   ODX_KERNEL_GAUSS     k = exp(-d^2 / (2 sigma^2))         (the limit nu -> inf)
+ *   ODX_KERNEL_MATERN32  k = (1 + u) exp(-u)                 (nu = 3/2)
+ *   ODX_KERNEL_MATERN52  k = (1 + u + u^2 / 3) exp(-u)       (nu = 5/2)
+ * The contraction X Z' does not depend on the kernel function and a value lies in (0, 1], so every storage format, the
+ * fused right-hand side and everything that reads a stored block serve all three.  The entries below take the arguments,
+ * workspaces (the siblings' queries) and errors of odx_gauss_knm_h2_store / odx_gauss_mmv_h2 / odx_gauss_mmvn_h2 /
+ * odx_falkon_precond_f64 / odx_falkon_precond_path_f64 plus `kind` behind sigma; an unknown kind is ODX_ERR_INVALID.  With
+ * ODX_KERNEL_GAUSS they ARE those siblings (the same launches, the same bits).  A Matern kind always runs on the 256 x 256
+ * tile core (scoring included, whatever odx_gauss_h2_tile says for the shape) with the split-f16 operands; K_MM of the
+ * preconditioner is evaluated in f64 (sqrt and exp in f64) as the Gaussian's is.  nu = 1/2 is not offered: its slope in
+ * d^2 is unbounded at 0, where the f32 evaluation of d^2 is off by up to 8e-4 for rows that are centres. */
+#define ODX_KERNEL_GAUSS 0
+#define ODX_KERNEL_MATERN32 1
+#define ODX_KERNEL_MATERN52 2
+int odx_radial_knm_h2_store(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                            const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                            double sigma, int kind, int fmt, void* K, int64_t ldk, void* Klo, int64_t ldlo, const double* w,
+                            double* ktw, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+int odx_radial_mmv_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                      const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D,
+                      double sigma, int kind, const double* V, int64_t ldv, const int32_t* ranges, int T,
+                      float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+int odx_radial_mmvn_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                       const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                       double sigma, int kind, const double* V, int64_t ldv, int T,
+                       float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+
 /* ---- Gaussian kernels on rows that are 16-bit already (bf16: is_bf16 = 1, f16: 0), at native width.
  * Operands are those of odx_gemm_b16 at 64-element granularity: plain row-major 16-bit rows, 16-byte aligned, row strides ldx /
  * ldz in ELEMENTS and multiples of 64 (one 128-byte stage), the columns D .. stride zero; no meta words, no scale.  A
@@ -470,6 +498,15 @@ int64_t odx_falkon_precond_path_workspace_bytes(int64_t M, int D, int L);
 int odx_falkon_precond_path_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
                                 double eps, double* LTi, double* LTit, double* LA, int64_t ld, int32_t* info,
                                 void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+/* Both for a radial kernel `kind` (ODX_KERNEL_*): K_MM is that kernel's, in f64 (sqrt and exp in f64); everything behind
+ * K_MM is the chain above.  Workspaces as above; ODX_KERNEL_GAUSS is the calls above, bit for bit. */
+int odx_falkon_precond_radial_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, int kind,
+                                  double lam, double eps, double* LTi, double* LTit, double* LAi,
+                                  double* LAit, int64_t ld, int32_t* info,
+                                  void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+int odx_falkon_precond_path_radial_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, int kind, const double* lams,
+                                       int L, double eps, double* LTi, double* LTit, double* LA, int64_t ld, int32_t* info,
+                                       void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 /* The same preconditioner for B <= 32 independent classes at once (the reference trains its classes one after the
  * other, OnlineRegionClassifier_incore.py:96-155 — each `classifier.train` call above builds one; the classes are
  * independent, so here every launch of the factorisation chain advances all B).  Z[b] / ldz[b] / M[b]: HOST arrays of

@@ -1248,18 +1248,24 @@ extern "C" int64_t odx_falkon_precond_workspace_bytes(int64_t M, int D) {
 
 // (one chain for a whole lambda path: everything up to T T'/M once, then per member l its own  + lams[l] I -> L_A -> inverses;
 // L = 1 is the plain preconditioner, factored in place)
-static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
+static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, int kind, const double* lams, int L,
                                    double eps, double* LTi, double* LTit, double* const* LAi, double* const* LAit, int64_t ld,
                                    int32_t* info, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
 
 // (Left alive, the idle helper streams of a class-batched chain slow every later small launch of the process: the caller
 // releases them when its fit / training step is queued, odx_release_helper_streams.)
+extern "C" int odx_falkon_precond_radial_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, int kind, double lam,
+                                             double eps, double* LTi, double* LTit, double* LAi, double* LAit, int64_t ld,
+                                             int32_t* info, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(LAi && LAit, "odx_falkon_precond_f64: null pointer");
+  const int rc = falkon_precond_f64_impl(Z, ldz, M, D, sigma, kind, &lam, 1, eps, LTi, LTit, &LAi, &LAit, ld, info, workspace, workspace_bytes, stream);
+  return rc;
+}
+
 extern "C" int odx_falkon_precond_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, double lam,
                                       double eps, double* LTi, double* LTit, double* LAi, double* LAit, int64_t ld,
                                       int32_t* info, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
-  ODX_REQUIRE(LAi && LAit, "odx_falkon_precond_f64: null pointer");
-  const int rc = falkon_precond_f64_impl(Z, ldz, M, D, sigma, &lam, 1, eps, LTi, LTit, &LAi, &LAit, ld, info, workspace, workspace_bytes, stream);
-  return rc;
+  return odx_falkon_precond_radial_f64(Z, ldz, M, D, sigma, ODX_KERNEL_GAUSS, lam, eps, LTi, LTit, LAi, LAit, ld, info, workspace, workspace_bytes, stream);
 }
 
 // The preconditioners of a lambda path: L_T, its inverses and T T'/M do not depend on lambda, so they are made once; member l
@@ -1270,9 +1276,9 @@ extern "C" int64_t odx_falkon_precond_path_workspace_bytes(int64_t M, int D, int
   return round_up(odx_falkon_precond_workspace_bytes(M, D), 16) + (L > 1 ? M * precond_ld(M) * (int64_t)sizeof(double) : 0);
 }
 
-extern "C" int odx_falkon_precond_path_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
-                                           double eps, double* LTi, double* LTit, double* LA, int64_t ld, int32_t* info,
-                                           void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+extern "C" int odx_falkon_precond_path_radial_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, int kind, const double* lams,
+                                                  int L, double eps, double* LTi, double* LTit, double* LA, int64_t ld, int32_t* info,
+                                                  void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
   ODX_REQUIRE(lams && LA && L >= 1 && L <= ODX_MAX_ZBATCH, "odx_falkon_precond_path_f64: 1 <= L <= %d lambdas, non-null lams / LA",
               ODX_MAX_ZBATCH);
   ODX_REQUIRE(M > 0 && ld >= M, "odx_falkon_precond_path_f64: bad sizes");
@@ -1282,12 +1288,19 @@ extern "C" int odx_falkon_precond_path_f64(const float* Z, int64_t ldz, int64_t 
     lai[l] = LA + (int64_t)(2 * l) * M * ld;
     lait[l] = lai[l] + M * ld;
   }
-  return falkon_precond_f64_impl(Z, ldz, M, D, sigma, lams, L, eps, LTi, LTit, lai, lait, ld, info, workspace, workspace_bytes, stream);
+  return falkon_precond_f64_impl(Z, ldz, M, D, sigma, kind, lams, L, eps, LTi, LTit, lai, lait, ld, info, workspace, workspace_bytes, stream);
 }
 
-static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
+extern "C" int odx_falkon_precond_path_f64(const float* Z, int64_t ldz, int64_t M, int D, double sigma, const double* lams, int L,
+                                           double eps, double* LTi, double* LTit, double* LA, int64_t ld, int32_t* info,
+                                           void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  return odx_falkon_precond_path_radial_f64(Z, ldz, M, D, sigma, ODX_KERNEL_GAUSS, lams, L, eps, LTi, LTit, LA, ld, info, workspace, workspace_bytes, stream);
+}
+
+static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D, double sigma, int kind, const double* lams, int L,
                                    double eps, double* LTi, double* LTit, double* const* LAi, double* const* LAit, int64_t ld,
                                    int32_t* info, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(kind == ODX_KERNEL_GAUSS || kind == ODX_KERNEL_MATERN32 || kind == ODX_KERNEL_MATERN52, "odx_falkon_precond_f64: unknown kernel kind %d", kind);
   ODX_REQUIRE(M > 0 && D > 0 && sigma > 0, "odx_falkon_precond_f64: bad sizes");
   ODX_REQUIRE(Z && LTi && LTit && info && workspace, "odx_falkon_precond_f64: null pointer");
   ODX_REQUIRE(ld % 2 == 0 && ld >= M && aligned16(LTi) && aligned16(LTit), "odx_falkon_precond_f64: outputs must be 16-byte aligned with even ld >= M");
@@ -1325,7 +1338,7 @@ static int falkon_precond_f64_impl(const float* Z, int64_t ldz, int64_t M, int D
   ODX_PROPAGATE(odx_convert_f32_f64(Z, ldz, Zd, ldzd, M, D, stream));
   // W0 = K_MM + eps*M*I (lower), then L_T in place
   ODX_CHECK_HIP(hipMemsetAsync(W0, 0, (size_t)(M * wld) * sizeof(double), s));
-  ODX_PROPAGATE(gauss_kmm_f64(Zd, ldzd, M, D, sigma, eps * (double)M, W0, wld, zsq, s));
+  ODX_PROPAGATE(gauss_kmm_f64(Zd, ldzd, M, D, sigma, eps * (double)M, W0, wld, zsq, s, kind));
   ODX_PROPAGATE(potrf_f64(W0, wld, M, DinvT, info, s));
   for (int l = 1; l < L; ++l)      // a failed pivot of L_T is every member's
     ODX_CHECK_HIP(hipMemcpyAsync(info + l, info, sizeof(int32_t), hipMemcpyDeviceToDevice, s));

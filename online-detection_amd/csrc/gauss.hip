@@ -223,6 +223,9 @@ __global__ __launch_bounds__(256) void row_sqnorm_f64_batched_kernel(const doubl
 // K_MM = exp(gamma max(0, |z_i|^2 + |z_j|^2 - 2 z_i.z_j)) (+ diag) on the lower triangle, in two steps: the Gram block
 // Z Z' by the f64 NT GEMM (128 x 64 tiles, three workgroups per CU: 60 TFLOP/s where the one-workgroup 128 x 128 tile
 // kernel above reaches 20), then this elementwise pass over the lower triangle (0.3 ms at M = 1e4).
+// KIND (ODX_KERNEL_*): a Matern kernel of the same d^2 instead, u = sqrt(2 nu d^2) / sigma = sqrt(-4 nu gamma d^2), with sqrt and
+// exp in f64 as the Gaussian's exp is: an f32 K_MM moves alpha by 2e-4 .. 5e-4.
+template <int KIND>
 __global__ __launch_bounds__(256) void kmm_epilogue_kernel(double* __restrict__ Kmm, int64_t ldk, int64_t k_stride,
                                                            const double* __restrict__ zsq, int64_t zsq_stride, VecBatch vb,
                                                            double gamma) {
@@ -233,13 +236,20 @@ __global__ __launch_bounds__(256) void kmm_epilogue_kernel(double* __restrict__ 
   double* g = Kmm + b * k_stride + row * ldk + col;
   double d2 = fma(-2.0, *g, zs[row]) + zs[col];
   d2 = fmax(d2, 0.0);
-  double v = exp(d2 * gamma);
+  double v;
+  if (KIND == ODX_KERNEL_GAUSS) {
+    v = exp(d2 * gamma);
+  } else {
+    const double u = sqrt((KIND == ODX_KERNEL_MATERN32 ? -6.0 : -10.0) * (d2 * gamma));
+    v = (KIND == ODX_KERNEL_MATERN32 ? 1.0 + u : 1.0 + u + u * u * (1.0 / 3.0)) * exp(-u);
+  }
   if (row == col) v += vb.scale[b];
   *g = v;
 }
 
 int gauss_kmm_f64_batched(const double* Zd, int64_t ldz, int64_t z_stride, int64_t zsq_off, const VecBatch& vb, int D,
-                          double sigma, double* Kmm, int64_t ldk, int64_t k_stride, hipStream_t stream) {
+                          double sigma, double* Kmm, int64_t ldk, int64_t k_stride, hipStream_t stream, int kind) {
+  ODX_REQUIRE(kind == ODX_KERNEL_GAUSS || kind == ODX_KERNEL_MATERN32 || kind == ODX_KERNEL_MATERN52, "gauss_kmm_f64: unknown kernel kind %d", kind);
   ODX_REQUIRE(ldz % 2 == 0 && z_stride % 2 == 0 && aligned16(Zd), "gauss_kmm_f64_batched: Zd must be 16-byte aligned, even strides");
   int mm = 0;
   for (int b = 0; b < vb.B; ++b) mm = vb.M[b] > mm ? vb.M[b] : mm;
@@ -253,21 +263,27 @@ int gauss_kmm_f64_batched(const double* Zd, int64_t ldz, int64_t z_stride, int64
   g.zbatches = vb.B; g.zstrideA = z_stride; g.zstrideB = z_stride; g.zstrideC = k_stride;
   ODX_PROPAGATE(launch_gemm_f64(g, stream));
   ODX_REQUIRE(mm < 65536, "gauss_kmm_f64: M must be below 65536");
-  hipLaunchKernelGGL(kmm_epilogue_kernel, dim3((unsigned)ceil_div(mm, 256), (unsigned)mm, (unsigned)vb.B), dim3(256), 0, stream,
-                     Kmm, ldk, k_stride, Zd + zsq_off, z_stride, vb, -0.5 / (sigma * sigma));
+  const dim3 grid((unsigned)ceil_div(mm, 256), (unsigned)mm, (unsigned)vb.B);
+  const double gamma = -0.5 / (sigma * sigma);
+  if (kind == ODX_KERNEL_MATERN32)
+    hipLaunchKernelGGL(kmm_epilogue_kernel<ODX_KERNEL_MATERN32>, grid, dim3(256), 0, stream, Kmm, ldk, k_stride, Zd + zsq_off, z_stride, vb, gamma);
+  else if (kind == ODX_KERNEL_MATERN52)
+    hipLaunchKernelGGL(kmm_epilogue_kernel<ODX_KERNEL_MATERN52>, grid, dim3(256), 0, stream, Kmm, ldk, k_stride, Zd + zsq_off, z_stride, vb, gamma);
+  else
+    hipLaunchKernelGGL(kmm_epilogue_kernel<ODX_KERNEL_GAUSS>, grid, dim3(256), 0, stream, Kmm, ldk, k_stride, Zd + zsq_off, z_stride, vb, gamma);
   ODX_CHECK_LAUNCH("kmm_epilogue");
   return ODX_OK;
 }
 
 // one class: Zd (M x ldz) with its squared norms written to zsq
 int gauss_kmm_f64(const double* Zd, int64_t ldz, int64_t M, int D, double sigma, double diag_add, double* Kmm,
-                  int64_t ldk, double* zsq, hipStream_t stream) {
+                  int64_t ldk, double* zsq, hipStream_t stream, int kind) {
   ODX_REQUIRE(ldz % 2 == 0 && aligned16(Zd), "gauss_kmm_f64: Zd must be 16-byte aligned with even ld");
   VecBatch vb;
   vb.B = 1;
   vb.M[0] = (int)M;
   vb.scale[0] = diag_add;
-  return gauss_kmm_f64_batched(Zd, ldz, 0, zsq - Zd, vb, D, sigma, Kmm, ldk, 0, stream);
+  return gauss_kmm_f64_batched(Zd, ldz, 0, zsq - Zd, vb, D, sigma, Kmm, ldk, 0, stream, kind);
 }
 
 // ---------------------------------------------------------------- small blocks by direct differences

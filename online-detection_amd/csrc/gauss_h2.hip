@@ -1199,13 +1199,33 @@ __device__ __forceinline__ unsigned short bf16_of(float v) {          // round t
   return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
+// The value of radial kernel KIND (ODX_KERNEL_*) from the Gaussian tiles' scaled exponent e = gamma log2(e) d^2 <= 0, gamma =
+// -1 / (2 sigma^2): the Gaussian is exp2(e).  For a Matern kind d^2 / sigma^2 = -2 ln(2) e, so u = sqrt(2 nu d^2) / sigma =
+// sqrt(-4 nu ln(2) e) needs no constant per width, and k = poly(u) exp2(-u log2(e)): a square root, an exp2 and three
+// (nu = 3/2) or four (nu = 5/2) f32 operations.  Both are smooth in d^2 at 0 (k = 1 - u^2 / 2 + ..., u^2 linear in d^2), slopes
+// 3 / (2 sigma^2) and 5 / (6 sigma^2) against the Gaussian's 1 / (2 sigma^2).  e = -inf gives inf * 0: callers that mark columns
+// that way select.
+template <int KIND>
+__device__ __forceinline__ float radial_value(float e) {
+  static_assert(KIND == ODX_KERNEL_GAUSS || KIND == ODX_KERNEL_MATERN32 || KIND == ODX_KERNEL_MATERN52, "unknown kernel kind");
+  if constexpr (KIND == ODX_KERNEL_GAUSS) {
+    return __builtin_amdgcn_exp2f(e);
+  } else {
+    constexpr float c = KIND == ODX_KERNEL_MATERN32 ? -4.1588830833596715f : -6.9314718055994531f;      // -4 nu ln(2)
+    const float u = __builtin_amdgcn_sqrtf(c * e);
+    const float p = KIND == ODX_KERNEL_MATERN32 ? 1.f + u : fmaf(u, fmaf(u, 0.33333333333333333f, 1.f), 1.f);
+    return p * __builtin_amdgcn_exp2f(u * -LOG2E);
+  }
+}
+
 // One lane's share of a tile's epilogue.  The exponent is formed already scaled, e = gamma log2(e) d^2 = fma(m2g, acc, xg) + zg
 // with the row / column norms pre-multiplied (xg in LDS, zg in registers; zg = -inf for the pad columns [M, mpad), which
-// are thereby stored as exp2(-inf) = 0 without a select): two operations per entry instead of three; the store addresses
+// are thereby stored as exp2(-inf) = 0 without a select — a Matern KIND would make inf * 0 of that and selects an exact
+// zero): two operations per entry instead of three; the store addresses
 // advance by the row pitch (the 64-bit products row * ld per store were a quarter-rate multiply chain of six instructions
 // per row); the two planes of the 24-bit format are cut out of the four words by two + three v_perm_b32 / v_or_b32.
 // `interior`: the tile lies inside the block, every store happens.
-template <bool RHS, int FMT>
+template <bool RHS, int FMT, int KIND = ODX_KERNEL_GAUSS>
 __device__ __forceinline__ void knm_tile_epilogue(const f32x4 (&acc)[8][4], const float* xg_s, const double* ws_s, int rl0,
                                                   float m2g, const float (&zg)[4], bool interior, bool cols_in,
                                                   int64_t rows_left, char* phi, int64_t shi, char* plo, int64_t slo,
@@ -1218,8 +1238,10 @@ __device__ __forceinline__ void knm_tile_epilogue(const f32x4 (&acc)[8][4], cons
       const double wq = RHS ? ws_s[rl0 + tm * 16 + q] : 0.0;
       f32x4 v;
 #pragma unroll
-      for (int tn = 0; tn < 4; ++tn)     // gamma < 0: d^2 >= 0 <=> e <= 0
-        v[tn] = __builtin_amdgcn_exp2f(fminf(fmaf(m2g, acc[tm][tn][q], xg[q]) + zg[tn], 0.f));
+      for (int tn = 0; tn < 4; ++tn) {   // gamma < 0: d^2 >= 0 <=> e <= 0
+        v[tn] = radial_value<KIND>(fminf(fmaf(m2g, acc[tm][tn][q], xg[q]) + zg[tn], 0.f));
+        if (KIND != ODX_KERNEL_GAUSS) v[tn] = zg[tn] == -__builtin_inff() ? 0.f : v[tn];      // pad columns: exact zeros
+      }
       const bool store = interior || (tm * 16 + q < rows_left && cols_in);
       if (FMT == KF_F32) {
         if (RHS) {
@@ -1264,7 +1286,8 @@ __device__ __forceinline__ void knm_tile_epilogue(const f32x4 (&acc)[8][4], cons
 // RHS: also leave wslab[row block][j] = sum over the tile's rows i of K_ij w_i (f64), K_ij being the value the block
 // STORES (the dequantised one for KF_U24 / KF_BF16): the column sums K' w of the right-hand side of the fit come out of
 // the build, and the first pass over the stored K_nM is not needed.
-template <bool RHS, int FMT, int CORE>
+// KIND: the radial kernel of the entries (radial_value; the Gaussian instantiations are the code they were before the parameter).
+template <bool RHS, int FMT, int CORE, int KIND = ODX_KERNEL_GAUSS>
 __global__ __launch_bounds__(W_THREADS, 1) void gauss_knm_h2w256_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
@@ -1301,7 +1324,7 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_knm_h2w256_kernel(
   const int esz = FMT == KF_F32 ? 4 : 2;
   char* phi = static_cast<char*>(Kp) + e0 * esz;
   char* plo = FMT == KF_U24 ? reinterpret_cast<char*>(Klo) + (i0 + rl0) * ldlo + j0 + cb : nullptr;
-  knm_tile_epilogue<RHS, FMT>(acc, xg_s, ws_s, rl0, m2g, zg, interior, cols_in, n - i0 - rl0, phi, ldk * esz, plo, ldlo, csum);
+  knm_tile_epilogue<RHS, FMT, KIND>(acc, xg_s, ws_s, rl0, m2g, zg, interior, cols_in, n - i0 - rl0, phi, ldk * esz, plo, ldlo, csum);
   if (RHS) {
     // lanes l, l + 16, l + 32, l + 48 hold the same columns: add them, then the two row halves of the tile through LDS
     double* red2 = reinterpret_cast<double*>(lds);          // the stage buffers are free: the main loop ended on a barrier
@@ -1949,7 +1972,9 @@ __global__ __launch_bounds__(W_THREADS, 1) void gemm_h2w256_f64_kernel(H2F64Para
 
 // Fused scoring on the 256 x 256 core: same decomposition as gauss_mmv_h2s16_kernel (row block x group of `tg` column
 // tiles, f64 partial row sums per group in the slab, mmv_reduce_kernel adds the groups), 256-row blocks, 256-column tiles.
-template <int CORE>
+// KIND: the radial kernel of the entries (radial_value).  Columns past the group / range have a finite exponent (their norm is
+// read as 0) and weight 0: no select is needed for them.
+template <int CORE, int KIND = ODX_KERNEL_GAUSS>
 __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmv_h2w256_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int stages,
@@ -2010,7 +2035,7 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmv_h2w256_kernel(
             // keeps them closer)
             float d2 = fmaf(m2, acc[tm][tn][q], xs) + zs[tn];
             d2 = fmaxf(d2, 0.f);
-            v[u] = fma((double)__builtin_amdgcn_exp2f(d2 * gamma_log2e), al[tn], v[u]);
+            v[u] = fma((double)radial_value<KIND>(d2 * gamma_log2e), al[tn], v[u]);
           }
         }
         w8[j] = QUARTER_STAGE(b8, v[0], v[1], 8);
@@ -2040,13 +2065,15 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmv_h2w256_kernel(
 // columns (there they die as they are read), so the column sums are kept out of the registers: see `park` and `mine`.
 // PERCOL: a kernel width per column (see gauss_mmvn_h2s16_kernel): the accumulators become the clamped squared distances,
 // the part of an entry every width shares, and each column takes its own exp2.
-template <int NV, int CORE, bool PERCOL>
+// KIND: the radial kernel of the entries (radial_value), with one width (PERCOL = false) only.
+template <int NV, int CORE, bool PERCOL, int KIND = ODX_KERNEL_GAUSS>
 __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_h2w256_kernel(
     const uint32_t* __restrict__ PX, int64_t ldpx, const float* __restrict__ metax, const float* __restrict__ xsq, int64_t n,
     const uint32_t* __restrict__ PZ, int64_t ldpz, const float* __restrict__ metaz, const float* __restrict__ zsq, int64_t M,
     int stages, MmvnGammas gm, const double* __restrict__ V, int64_t ldv, int cbase, int T, int tg, int G,
     double* __restrict__ slab, int64_t slab_ld) {
 #pragma clang fp contract(off)
+  static_assert(!PERCOL || KIND == ODX_KERNEL_GAUSS, "a width per column is Gaussian-only");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ __attribute__((aligned(16))) float xs_s[W_BM];
   // The sums of the first PARK columns stay in LDS of their own for the whole kernel: 3 x 8 KiB is what the CU has left
@@ -2108,7 +2135,7 @@ __global__ __launch_bounds__(W_THREADS, 1) void gauss_mmvn_h2w256_kernel(
         for (int tn = 0; tn < 4; ++tn) {    // (the form of gauss_mmv_h2w256_kernel: its bits are the contract)
           float d2 = fmaf(m2, acc[tm][tn][q], xs) + zs[tn];
           d2 = fmaxf(d2, 0.f);
-          acc[tm][tn][q] = PERCOL ? d2 : __builtin_amdgcn_exp2f(d2 * gm.g[0]);
+          acc[tm][tn][q] = PERCOL ? d2 : radial_value<KIND>(d2 * gm.g[0]);
         }
       }
 #pragma unroll
@@ -2330,13 +2357,21 @@ static int knm_rhs_fmt(bool rhs, int kf, L&& launch) {
 constexpr int W_KNM_GR = 4;
 static int64_t knm_w256_grid(int64_t n, int64_t M) { return round_up(ceil_div(n, W_BM), W_KNM_GR) * ceil_div(M, W_BN); }
 
-template <bool RHS, int FMT, int CORE>
+// The radial kernels (ODX_KERNEL_*) as the wide kernels' KIND: f(kind as an integral constant).  The Matern kinds exist on the
+// 256 x 256 core with the split-f16 operands only; the entries check the kind before they get here.
+static bool radial_kind_known(int kind) { return kind == ODX_KERNEL_GAUSS || kind == ODX_KERNEL_MATERN32 || kind == ODX_KERNEL_MATERN52; }
+template <typename L>
+static int with_matern_kind(int kind, L&& f) {
+  return kind == ODX_KERNEL_MATERN32 ? f(IntC<ODX_KERNEL_MATERN32>()) : f(IntC<ODX_KERNEL_MATERN52>());
+}
+
+template <bool RHS, int FMT, int CORE, int KIND = ODX_KERNEL_GAUSS>
 static int launch_knm_w256_t(unsigned wt, hipStream_t s, const uint32_t* PX, int64_t ldpx, const float* metax, const float* xsq,
                              int64_t n, const uint32_t* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M,
                              int stages, float g2, void* K, int64_t ldk, unsigned char* Klo, int64_t ldlo, int wgr,
                              const double* w, double* wslab, int64_t wslab_ld) {
-  ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_knm_h2w256_kernel<RHS, FMT, CORE>), W_LDS_BYTES));
-  hipLaunchKernelGGL((gauss_knm_h2w256_kernel<RHS, FMT, CORE>), dim3(wt), dim3(W_THREADS), W_LDS_BYTES, s, PX, ldpx, metax,
+  ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_knm_h2w256_kernel<RHS, FMT, CORE, KIND>), W_LDS_BYTES));
+  hipLaunchKernelGGL((gauss_knm_h2w256_kernel<RHS, FMT, CORE, KIND>), dim3(wt), dim3(W_THREADS), W_LDS_BYTES, s, PX, ldpx, metax,
                      xsq, n, PZ, ldpz, metaz, zsq, M, stages, g2, K, ldk, Klo, ldlo, wgr, w, wslab, wslab_ld);
   return ODX_OK;
 }
@@ -2347,9 +2382,10 @@ static int launch_knm_w256_t(unsigned wt, hipStream_t s, const uint32_t* PX, int
 static int launch_knm_w256(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
                            int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int stages, double sigma, int fmt,
                            void* K, int64_t ldk, void* Klo, int64_t ldlo, const double* w, double* wslab, int64_t wslab_ld,
-                           odx_stream_t stream, int core = CORE_H2) {
+                           odx_stream_t stream, int core = CORE_H2, int kind = ODX_KERNEL_GAUSS) {
   const int64_t wt = knm_w256_grid(n, M);
   ODX_REQUIRE(wt < (1ll << 31), "odx_gauss_knm_h2: grid too large");
+  ODX_REQUIRE(kind == ODX_KERNEL_GAUSS || core == CORE_H2, "odx_gauss_knm_h2: a Matern kernel needs the split-f16 operands");
   const float g2 = h2_gamma_log2e(sigma);
   hipStream_t s = as_stream(stream);
   const uint32_t *px = (const uint32_t*)PX, *pz = (const uint32_t*)PZ;
@@ -2357,6 +2393,11 @@ static int launch_knm_w256(const void* PX, int64_t ldpx, const float* metax, con
   ODX_PROPAGATE(knm_rhs_fmt(w != nullptr, fmt, [&](auto rhs, auto kf) {
     constexpr bool RHS = decltype(rhs)::value;
     constexpr int FMT = decltype(kf)::value;
+    if (kind != ODX_KERNEL_GAUSS)
+      return with_matern_kind(kind, [&](auto k) {
+        return launch_knm_w256_t<RHS, FMT, CORE_H2, decltype(k)::value>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M,
+                                                                        stages, g2, K, ldk, lo, ldlo, W_KNM_GR, w, wslab, wslab_ld);
+      });
     auto run = [&](auto c) {
       return launch_knm_w256_t<RHS, FMT, decltype(c)::value>((unsigned)wt, s, px, ldpx, metax, xsq, n, pz, ldpz, metaz, zsq, M, stages, g2, K,
                                                              ldk, lo, ldlo, W_KNM_GR, w, wslab, wslab_ld);
@@ -2888,7 +2929,8 @@ static int check_b16_pair(const char* who, int D, int64_t ldx, int64_t ldz, cons
 static int knm_store_impl(const char* who, int core, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
                           const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma,
                           int fmt, void* K, int64_t ldk, void* Klo, int64_t ldlo, const double* w, double* ktw, void* workspace,
-                          int64_t workspace_bytes, odx_stream_t stream) {
+                          int64_t workspace_bytes, odx_stream_t stream, int kind = ODX_KERNEL_GAUSS) {
+  ODX_REQUIRE(radial_kind_known(kind), "%s: unknown kernel kind %d", who, kind);
   ODX_REQUIRE(M > 0, "%s: M <= 0", who);
   ODX_REQUIRE(fmt == ODX_KNM_F32 || fmt == ODX_KNM_U24 || fmt == ODX_KNM_BF16, "%s: unknown storage format %d", who, fmt);
   ODX_REQUIRE((w == nullptr) == (ktw == nullptr), "%s: w and ktw go together", who);
@@ -2905,7 +2947,7 @@ static int knm_store_impl(const char* who, int core, const void* PX, int64_t ldp
   }
   const int64_t wld = round_up(M, 4);
   ODX_PROPAGATE(launch_knm_w256(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, core_stages(D, core), sigma, fmt, K, ldk, Klo, ldlo,
-                                w, static_cast<double*>(workspace), wld, stream, core));
+                                w, static_cast<double*>(workspace), wld, stream, core, kind));
   if (w == nullptr) return ODX_OK;
   return slab_reduce_f64(static_cast<const double*>(workspace), wld, (int)ceil_div(n, W_BM), M, ktw, as_stream(stream));
 }
@@ -2916,6 +2958,14 @@ extern "C" int odx_gauss_knm_h2_store(const void* PX, int64_t ldpx, const float*
                                       double* ktw, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
   return knm_store_impl("odx_gauss_knm_h2_store", CORE_H2, PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, fmt, K, ldk,
                         Klo, ldlo, w, ktw, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_radial_knm_h2_store(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                                       const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D,
+                                       double sigma, int kind, int fmt, void* K, int64_t ldk, void* Klo, int64_t ldlo, const double* w,
+                                       double* ktw, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  return knm_store_impl("odx_radial_knm_h2_store", CORE_H2, PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, fmt, K, ldk,
+                        Klo, ldlo, w, ktw, workspace, workspace_bytes, stream, kind);
 }
 
 // ---- rows that are 16-bit already (bf16 / f16): the Gaussian kernels at native width
@@ -3154,7 +3204,7 @@ extern "C" int64_t odx_gauss_mmv_h2_workspace_bytes(int64_t n, int64_t max_range
   return (int64_t)T * mmv_groups(max_range, mmv_tg(n, max_range, T)) * round_up(n, 2) * (int64_t)sizeof(double);
 }
 
-template <int CORE>
+template <int CORE, int KIND = ODX_KERNEL_GAUSS>
 static int launch_mmv_w256(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
                            int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int stages, double sigma,
                            const double* V, int64_t ldv, const int32_t* ranges, int C, float* out, int64_t ldo, double* slab,
@@ -3162,8 +3212,8 @@ static int launch_mmv_w256(const void* PX, int64_t ldpx, const float* metax, con
   const int64_t Gw = ceil_div(ceil_div(max_range, W_BN), W_MMV_TG);      // <= mmv_groups(max_range): the slab is large enough
   const int64_t wgs = round_up(ceil_div(n, W_BM), 8) * Gw;
   ODX_REQUIRE(wgs < (1ll << 31), "odx_gauss_mmv: grid too large");
-  ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmv_h2w256_kernel<CORE>), W_LDS_BYTES));
-  hipLaunchKernelGGL((gauss_mmv_h2w256_kernel<CORE>), dim3((unsigned)wgs, (unsigned)C), dim3(W_THREADS), W_LDS_BYTES,
+  ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmv_h2w256_kernel<CORE, KIND>), W_LDS_BYTES));
+  hipLaunchKernelGGL((gauss_mmv_h2w256_kernel<CORE, KIND>), dim3((unsigned)wgs, (unsigned)C), dim3(W_THREADS), W_LDS_BYTES,
                      as_stream(stream), (const uint32_t*)PX, ldpx, metax, xsq, n, (const uint32_t*)PZ, ldpz, metaz, zsq, stages,
                      h2_gamma_log2e(sigma), V, ldv, ranges, W_MMV_TG, (int)Gw, slab, slab_ld);
   ODX_CHECK_LAUNCH("odx_gauss_mmv(w256)");
@@ -3179,7 +3229,7 @@ static int launch_mmv_w256(const void* PX, int64_t ldpx, const float* metax, con
 static int mmv_ranges_run(const char* who, int core, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
                           const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D, double sigma,
                           const double* V, int64_t ldv, const int32_t* ranges, int C, float* out, int64_t ldo, void* workspace,
-                          int64_t workspace_bytes, odx_stream_t stream) {
+                          int64_t workspace_bytes, odx_stream_t stream, int kind = ODX_KERNEL_GAUSS) {
   ODX_REQUIRE(ldo >= C && C < 65536, "%s: ldo < C or too many classes", who);
   if (workspace == nullptr || workspace_bytes < odx_gauss_mmv_h2_workspace_bytes(n, max_range, C)) {
     set_error("%s: workspace too small", who);
@@ -3188,6 +3238,13 @@ static int mmv_ranges_run(const char* who, int core, const void* PX, int64_t ldp
   double* slab = static_cast<double*>(workspace);
   const int64_t slab_ld = round_up(n, 2);
   const int stages = core_stages(D, core);             // 128-byte pieces of an operand row; a k-tile of the 128 x 128 core is two
+  if (kind != ODX_KERNEL_GAUSS) {      // a Matern kind: the wide core at every shape (its groups never outnumber the slab's: launch_mmv_w256)
+    ODX_REQUIRE(core == CORE_H2, "%s: a Matern kernel needs the split-f16 operands", who);
+    return with_matern_kind(kind, [&](auto k) {
+      return launch_mmv_w256<CORE_H2, decltype(k)::value>(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, stages, sigma, V, ldv,
+                                                          ranges, C, out, ldo, slab, slab_ld, stream);
+    });
+  }
   if (h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(max_range, W_BN), W_MMV_TG) * C)) {
     auto run = [&](auto c) {
       return launch_mmv_w256<decltype(c)::value>(PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, stages, sigma, V, ldv, ranges, C,
@@ -3215,16 +3272,33 @@ static int mmv_ranges_run(const char* who, int core, const void* PX, int64_t ldp
   return ODX_OK;
 }
 
+static int mmv_h2_entry(const char* who, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
+                        int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D, double sigma, int kind,
+                        const double* V, int64_t ldv, const int32_t* ranges, int C, float* out, int64_t ldo, void* workspace,
+                        int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(radial_kind_known(kind), "%s: unknown kernel kind %d", who, kind);
+  if (n <= 0 || C <= 0) return ODX_OK;
+  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && ranges && out && D > 0 && sigma > 0 && ldv >= C && max_range > 0,
+              "%s: bad argument", who);
+  ODX_PROPAGATE(check_packed_pair(who, round_up(D, H2_KT), ldpx, ldpz, PX, PZ));
+  return mmv_ranges_run(who, CORE_H2, PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, D, sigma, V, ldv, ranges, C,
+                        out, ldo, workspace, workspace_bytes, stream, kind);
+}
+
 extern "C" int odx_gauss_mmv_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
                                 const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D,
                                 double sigma, const double* V, int64_t ldv, const int32_t* ranges, int C, float* out,
                                 int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
-  if (n <= 0 || C <= 0) return ODX_OK;
-  ODX_REQUIRE(PX && PZ && metax && metaz && xsq && zsq && V && ranges && out && D > 0 && sigma > 0 && ldv >= C && max_range > 0,
-              "odx_gauss_mmv_h2: bad argument");
-  ODX_PROPAGATE(check_packed_pair("odx_gauss_mmv_h2", round_up(D, H2_KT), ldpx, ldpz, PX, PZ));
-  return mmv_ranges_run("odx_gauss_mmv_h2", CORE_H2, PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, D, sigma, V, ldv, ranges, C,
-                        out, ldo, workspace, workspace_bytes, stream);
+  return mmv_h2_entry("odx_gauss_mmv_h2", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, D, sigma, ODX_KERNEL_GAUSS, V, ldv,
+                      ranges, C, out, ldo, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_radial_mmv_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n,
+                                 const void* PZ, int64_t ldpz, const float* metaz, const float* zsq, int64_t max_range, int D,
+                                 double sigma, int kind, const double* V, int64_t ldv, const int32_t* ranges, int C, float* out,
+                                 int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  return mmv_h2_entry("odx_radial_mmv_h2", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, max_range, D, sigma, kind, V, ldv, ranges, C,
+                      out, ldo, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t odx_gauss_mmv_b16_workspace_bytes(int64_t n, int64_t max_range, int T) {
@@ -3253,16 +3327,17 @@ struct MmvnArgs {
   double* slab;
   int kt, T, tg, G;          // kt: k-tiles (128 x 128 core) or stages (256 x 256 core)
   int core, half_tail;       // CORE_H2, or CORE_BF16 / CORE_F16 (plain 16-bit rows, one width); 128 x 128 core: the last k-tile is half a one
+  int kind;                  // ODX_KERNEL_*; a Matern kind: CORE_H2, the wide core, one width
   unsigned wgs;
   hipStream_t stream;
 };
 
 // `groups` groups of NV columns from column cbase on
-template <int NV, bool WIDE, bool PERCOL, int CORE>
+template <int NV, bool WIDE, bool PERCOL, int CORE, int KIND = ODX_KERNEL_GAUSS>
 static int launch_mmvn_group_core(const MmvnArgs& a, const MmvnGammas& gm, int cbase, int groups) {
   if (WIDE) {
-    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2w256_kernel<NV, CORE, PERCOL>), W_LDS_BYTES));
-    hipLaunchKernelGGL((gauss_mmvn_h2w256_kernel<NV, CORE, PERCOL>), dim3(a.wgs, (unsigned)groups), dim3(W_THREADS), W_LDS_BYTES,
+    ODX_PROPAGATE(h2_enable_lds(reinterpret_cast<const void*>(gauss_mmvn_h2w256_kernel<NV, CORE, PERCOL, KIND>), W_LDS_BYTES));
+    hipLaunchKernelGGL((gauss_mmvn_h2w256_kernel<NV, CORE, PERCOL, KIND>), dim3(a.wgs, (unsigned)groups), dim3(W_THREADS), W_LDS_BYTES,
                        a.stream, a.PX, a.ldpx, a.metax, a.xsq, a.n, a.PZ, a.ldpz, a.metaz, a.zsq, a.M, a.kt, gm, a.V, a.ldv, cbase, a.T,
                        a.tg, a.G, a.slab, a.slab_ld);
   } else {
@@ -3277,6 +3352,12 @@ static int launch_mmvn_group_core(const MmvnArgs& a, const MmvnGammas& gm, int c
 
 template <int NV, bool WIDE, bool PERCOL>
 static int launch_mmvn_group(const MmvnArgs& a, const MmvnGammas& gm, int cbase, int groups) {
+  if constexpr (!PERCOL && WIDE) {  // (a Matern kind: the wide core, the split rows, one width: mmvn_run)
+    if (a.kind != ODX_KERNEL_GAUSS)
+      return with_matern_kind(a.kind, [&](auto k) {
+        return launch_mmvn_group_core<NV, true, false, CORE_H2, decltype(k)::value>(a, gm, cbase, groups);
+      });
+  }
   if constexpr (!PERCOL) {          // (a width per column exists for the split rows only: mmvn_run)
     if (a.core == CORE_BF16) return launch_mmvn_group_core<NV, WIDE, false, CORE_BF16>(a, gm, cbase, groups);
     if (a.core == CORE_F16) return launch_mmvn_group_core<NV, WIDE, false, CORE_F16>(a, gm, cbase, groups);
@@ -3316,8 +3397,9 @@ static int launch_mmvn(const MmvnArgs& a, double sigma, const double* sigmas) {
 static int mmvn_run(const char* who, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
                     int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma, const double* sigmas,
                     const double* V, int64_t ldv, int T, float* out, int64_t ldo, void* workspace, int64_t workspace_bytes,
-                    odx_stream_t stream, int core = CORE_H2) {
+                    odx_stream_t stream, int core = CORE_H2, int kind = ODX_KERNEL_GAUSS) {
   ODX_REQUIRE(PX && PZ && ((metax && metaz) || core_is_b16(core)) && xsq && zsq && V && out && D > 0 && ldv >= T && M > 0, "%s: bad argument", who);
+  ODX_REQUIRE(kind == ODX_KERNEL_GAUSS || (core == CORE_H2 && sigmas == nullptr), "%s: a Matern kernel needs the split-f16 operands and one width", who);
   ODX_REQUIRE(!(core_is_b16(core) && sigmas), "%s: a width per column needs the split rows", who);
   const int stages = core_stages(D, core);            // 128-byte pieces of an operand row; a k-tile of the 128 x 128 core is two
   ODX_PROPAGATE(check_packed_pair(who, core_min_ld(D, core), ldpx, ldpz, PX, PZ));
@@ -3328,9 +3410,10 @@ static int mmvn_run(const char* who, const void* PX, int64_t ldpx, const float* 
   }
   MmvnArgs a;
   a.who = who, a.PX = (const uint32_t*)PX, a.PZ = (const uint32_t*)PZ, a.ldpx = ldpx, a.ldpz = ldpz, a.n = n, a.M = M, a.ldv = ldv;
-  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T, a.core = core, a.half_tail = 0;
+  a.metax = metax, a.xsq = xsq, a.metaz = metaz, a.zsq = zsq, a.V = V, a.T = T, a.core = core, a.half_tail = 0, a.kind = kind;
   a.slab = static_cast<double*>(workspace), a.slab_ld = round_up(n, 2), a.stream = as_stream(stream);
-  const bool wide = h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
+  // (a Matern kind: the wide core at every shape; its groups never outnumber the slab's, as in launch_mmv_w256)
+  const bool wide = kind != ODX_KERNEL_GAUSS || h2_use_w256(ceil_div(n, W_BM) * ceil_div(ceil_div(M, W_BN), W_MMV_TG) * T);
   int64_t wgs;
   if (wide) {
     a.tg = W_MMV_TG, a.G = (int)ceil_div(ceil_div(M, W_BN), W_MMV_TG), a.kt = stages;
@@ -3352,14 +3435,30 @@ extern "C" int64_t odx_gauss_mmvn_h2_workspace_bytes(int64_t n, int64_t M, int T
   return odx_gauss_mmv_h2_workspace_bytes(n, M, T);
 }
 
+static int mmvn_h2_entry(const char* who, const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
+                         int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma, int kind, const double* V,
+                         int64_t ldv, int T, float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, odx_stream_t stream) {
+  ODX_REQUIRE(radial_kind_known(kind), "%s: unknown kernel kind %d", who, kind);
+  if (n <= 0 || T <= 0) return ODX_OK;
+  ODX_REQUIRE(sigma > 0, "%s: bad argument", who);
+  return mmvn_run(who, PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, nullptr, V, ldv, T, out, ldo, workspace, workspace_bytes,
+                  stream, CORE_H2, kind);
+}
+
 extern "C" int odx_gauss_mmvn_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
                                  int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma,
                                  const double* V, int64_t ldv, int T, float* out, int64_t ldo, void* workspace,
                                  int64_t workspace_bytes, odx_stream_t stream) {
-  if (n <= 0 || T <= 0) return ODX_OK;
-  ODX_REQUIRE(sigma > 0, "odx_gauss_mmvn_h2: bad argument");
-  return mmvn_run("odx_gauss_mmvn_h2", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, nullptr, V, ldv, T, out, ldo,
-                  workspace, workspace_bytes, stream);
+  return mmvn_h2_entry("odx_gauss_mmvn_h2", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, ODX_KERNEL_GAUSS, V, ldv, T, out, ldo,
+                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int odx_radial_mmvn_h2(const void* PX, int64_t ldpx, const float* metax, const float* xsq, int64_t n, const void* PZ,
+                                  int64_t ldpz, const float* metaz, const float* zsq, int64_t M, int D, double sigma, int kind,
+                                  const double* V, int64_t ldv, int T, float* out, int64_t ldo, void* workspace,
+                                  int64_t workspace_bytes, odx_stream_t stream) {
+  return mmvn_h2_entry("odx_radial_mmvn_h2", PX, ldpx, metax, xsq, n, PZ, ldpz, metaz, zsq, M, D, sigma, kind, V, ldv, T, out, ldo,
+                       workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t odx_gauss_mmvn_b16_workspace_bytes(int64_t n, int64_t M, int T) { return odx_gauss_mmv_h2_workspace_bytes(n, M, T); }

@@ -153,11 +153,11 @@ int gemm_h2_f64(const uint32_t* PA, int64_t ldpa, int64_t zsa, float sa, const u
                 double* C, int64_t ldc, int64_t zsc, int64_t m, int64_t n, int64_t k, const double* alpha, double beta, int flags,
                 int zcount, hipStream_t stream);
 
-// gauss.hip
+// gauss.hip (kind: the radial kernel of K_MM, ODX_KERNEL_*)
 int gauss_kmm_f64(const double* Zd, int64_t ldz, int64_t M, int D, double sigma, double diag_add, double* Kmm,
-                  int64_t ldk, double* zsq /* M */, hipStream_t stream);
+                  int64_t ldk, double* zsq /* M */, hipStream_t stream, int kind = ODX_KERNEL_GAUSS);
 
 int gauss_kmm_f64_batched(const double* Zd, int64_t ldz, int64_t z_stride, int64_t zsq_off, const VecBatch& vb, int D,
-                          double sigma, double* Kmm, int64_t ldk, int64_t k_stride, hipStream_t stream);
+                          double sigma, double* Kmm, int64_t ldk, int64_t k_stride, hipStream_t stream, int kind = ODX_KERNEL_GAUSS);
 
 }  // namespace odx

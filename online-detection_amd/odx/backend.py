@@ -477,7 +477,13 @@ class HipBackend(PathOps):
         P.info = torch.zeros(1, dtype=torch.int32, device=self.device)
         nbytes = self.lib.odx_falkon_precond_workspace_bytes(M, D)
         ws = self._workspace(ws_key, nbytes)
-        hip.check(self.lib.odx_falkon_precond_f64(_p(Zf.X), Zf.ld, M, D, float(sigma), float(lam), float(eps),
+        sigma, kind = hip.radial_of(sigma)
+        if kind:             # a Matern kernel object: K_MM is that kernel's, the chain behind it the same
+            hip.check(self.lib.odx_falkon_precond_radial_f64(_p(Zf.X), Zf.ld, M, D, sigma, kind, float(lam), float(eps),
+                                                             _p(P.LTi), _p(P.LTit), _p(P.LAi), _p(P.LAit), ld, _p(P.info),
+                                                             _p(ws), ws.numel(), self._stream()), "odx_falkon_precond_radial_f64")
+            return P
+        hip.check(self.lib.odx_falkon_precond_f64(_p(Zf.X), Zf.ld, M, D, sigma, float(lam), float(eps),
                                                   _p(P.LTi), _p(P.LTit), _p(P.LAi), _p(P.LAit), ld, _p(P.info),
                                                   _p(ws), ws.numel(), self._stream()), "odx_falkon_precond_f64")
         return P
@@ -588,8 +594,21 @@ class HipBackend(PathOps):
                 K.lo = raw[n * ld * 2: n * ld * 3].view(n, ld)
         return K
 
+    def _matern_refuse(self, what, F, Zf):
+        """A Matern kernel exists on the split-f16 wide tile core only (odx_radial_*): refuse, by name, every route that
+        would otherwise evaluate a Gaussian — the f32 / f8 kernels, the streamed shard, the native 16-bit kernels."""
+        if self.gauss != "h2":
+            raise NotImplementedError("%s: a Matern kernel needs gauss 'h2' (the split-f16 wide tile core); gauss is %r" % (what, self.gauss))
+        if self.knm_storage == "stream":
+            raise NotImplementedError("%s: a Matern kernel with knm_storage 'stream' (the streamed pass recomputes a Gaussian)" % what)
+        if self._native16_pair(F, Zf):
+            raise NotImplementedError("%s: a Matern kernel on 16-bit rows at native width (native16); pass f32 rows" % what)
+
     def knm(self, F, Zf, sigma, out=None):
         n, M = F.n, Zf.n
+        if hip.radial_of(sigma)[1]:          # a Matern kernel object: the wide core's store build at every shape, never direct_small
+            self._matern_refuse("knm", F, Zf)
+            return self._knm_store(F, Zf, sigma, self.knm_format(n, M), None, out, None)[0]
         fmt = self.knm_format(n, M)
         if fmt == "stream":
             raise ValueError("knm: knm_storage 'stream' stores no K_nM block (knm_rhs hands out a streamed shard)")
@@ -629,6 +648,9 @@ class HipBackend(PathOps):
         """Build on the wide tile core into storage format `fmt` (odx_gauss_knm_h2_store), with the fused right-hand side
         when w is given."""
         n, M = F.n, Zf.n
+        sigma, kind = hip.radial_of(sigma)
+        if kind:
+            self._matern_refuse("knm_store", F, Zf)
         K = self._knm_block(n, M, fmt, out)
         f8 = self.gauss == "f8"
         native = self._native16_pair(F, Zf)
@@ -648,6 +670,12 @@ class HipBackend(PathOps):
                                                        K.ld, _p(K.lo), K.ld, _p(w), _p(rhs_out if w is not None else None), _p(ws),
                                                        ws.numel() if ws is not None else 0, self._stream()), "odx_gauss_knm_b16_store")
             return K, rhs_out
+        if kind:            # a Matern kernel: the same build with that kernel's epilogue (the siblings' workspace)
+            hip.check(self.lib.odx_radial_knm_h2_store(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), n, _p(Zf.P), Zf.P.stride(0), _p(Zf.meta),
+                                                       _p(Zf.sq), M, F.D, sigma, kind, hip.KNM_CODE[fmt], _p(K.K), K.ld, _p(K.lo), K.ld,
+                                                       _p(w), _p(rhs_out if w is not None else None), _p(ws),
+                                                       ws.numel() if ws is not None else 0, self._stream()), "odx_radial_knm_h2_store")
+            return K, rhs_out
         fn, PX, mx, PZ, mz = ((self.lib.odx_gauss_knm_f8_store, F.P8, F.meta8, Zf.P8, Zf.meta8) if f8 else
                               (self.lib.odx_gauss_knm_h2_store, F.P, F.meta, Zf.P, Zf.meta))
         sqx, sqz = (F.sq8, Zf.sq8) if f8 else (F.sq, Zf.sq)
@@ -663,6 +691,9 @@ class HipBackend(PathOps):
         n, M = F.n, Zf.n
         if rhs_out is None:
             rhs_out = torch.empty(M, dtype=torch.float64, device=self.device)
+        matern = hip.radial_of(sigma)[1] != hip.KERNEL_GAUSS
+        if matern:           # (before knm_format: 'stream' with another gauss is its ValueError, a Matern kernel is refused either way)
+            self._matern_refuse("knm_rhs", F, Zf)
         fmt = self.knm_format(n, M)
         if not self._native16_pair(F, Zf) or fmt == "stream":
             F, Zf = self.f32(F), self.f32(Zf)
@@ -689,7 +720,7 @@ class HipBackend(PathOps):
             if w is not None:
                 self._call("odx_cols_expand_f64", _p(b_d), K.M, _p(col_of), M, _p(rhs_out))
             return K, rhs_out
-        if (fmt != "f32" or self.gauss == "f8") and n > 0:
+        if (fmt != "f32" or self.gauss == "f8" or matern) and n > 0:      # (a Matern kernel: the store build at every shape)
             return self._knm_store(F, Zf, sigma, fmt, w, out, rhs_out)
         if not (self.gauss == "h2" and n > 0 and self.lib.odx_gauss_h2_tile(n, M) == 256) or self.direct_small(n, M, F.D):
             K = self.knm(F, Zf, sigma, out=out)
@@ -903,6 +934,9 @@ class HipBackend(PathOps):
         Mtot, T = V.shape
         if Mtot != Zf.n:
             raise ValueError("mmv: V has %d rows but there are %d centres" % (Mtot, Zf.n))
+        sigma, kind = hip.radial_of(sigma)
+        if kind:             # a Matern kernel object: the wide core's scoring kernels on the split rows, nothing else
+            self._matern_refuse("mmv", F, Zf)
         native = self._native16_pair(F, Zf)          # 16-bit rows of one type: scored as they are; every other mix in f32
         if not native:
             F, Zf = self.f32(F), self.f32(Zf)
@@ -922,6 +956,11 @@ class HipBackend(PathOps):
                                                       self._stream()), "odx_gauss_mmvn_b16")
                 return out
             self.pack(F), self.pack(Zf)
+            if kind:
+                hip.check(self.lib.odx_radial_mmvn_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), F.n, _p(Zf.P), Zf.P.stride(0),
+                                                      _p(Zf.meta), _p(Zf.sq), Mtot, F.D, sigma, kind, _p(V), V.stride(0), T,
+                                                      _p(out), out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_radial_mmvn_h2")
+                return out
             hip.check(self.lib.odx_gauss_mmvn_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), F.n, _p(Zf.P), Zf.P.stride(0),
                                                  _p(Zf.meta), _p(Zf.sq), Mtot, F.D, float(sigma), _p(V), V.stride(0), T,
                                                  _p(out), out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_mmvn_h2")
@@ -955,6 +994,11 @@ class HipBackend(PathOps):
             self.pack(F), self.pack(Zf)
             mr = Mtot if max_range is None else max(1, min(int(max_range), Mtot))
             ws = self._workspace("mmv", self.lib.odx_gauss_mmv_h2_workspace_bytes(F.n, mr, T))
+            if kind:
+                hip.check(self.lib.odx_radial_mmv_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), F.n, _p(Zf.P), Zf.P.stride(0),
+                                                     _p(Zf.meta), _p(Zf.sq), mr, F.D, sigma, kind, _p(V), V.stride(0), _p(ranges), T,
+                                                     _p(out), out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_radial_mmv_h2")
+                return out
             hip.check(self.lib.odx_gauss_mmv_h2(_p(F.P), F.P.stride(0), _p(F.meta), _p(F.sq), F.n, _p(Zf.P), Zf.P.stride(0),
                                                 _p(Zf.meta), _p(Zf.sq), mr, F.D, float(sigma), _p(V), V.stride(0), _p(ranges), T,
                                                 _p(out), out.stride(0), _p(ws), ws.numel(), self._stream()), "odx_gauss_mmv_h2")

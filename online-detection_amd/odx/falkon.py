@@ -43,12 +43,14 @@ class FalkonOptions:
                              cg_tolerance=self.cg_tolerance, cg_full_gradient_every=self.cg_full_gradient_every)
 
 
-class GaussianKernel:
-    """K(x, z) = exp(-|x - z|^2 / (2 sigma^2)); ``mmv`` is the fused scoring kernel."""
-    kernel_name = "gaussian"
+class _RadialKernel:
+    """A radial kernel of the backend (`kind`: ODX_KERNEL_* of include/odx.h) with falkon's ``mmv``."""
+    kind = 0
 
-    def __init__(self, sigma, opt=None):
-        self.sigma = float(sigma)
+    def _arg(self):
+        """What the backend wrappers get as `sigma`: the width itself for the Gaussian (the same float as ever), the kernel
+        object for any other kind — a wrapper that does not know the kinds fails at its float(sigma)."""
+        return self.sigma if self.kind == 0 else self
 
     def mmv(self, X1, X2, v, out=None, opt=None, dense=False):
         """K(X1, X2) @ v -> (n, T) f32.  A block-structured v (the heads' alpha_parallel) is
@@ -63,14 +65,59 @@ class GaussianKernel:
         if v.dim() == 1:
             v = v[:, None]
         ranges = block_ranges(v) if v.shape[1] > 1 and not dense else None      # one column (model.predict): every centre counts
-        res = be.mmv(F, Zf, self.sigma, v, ranges)
+        res = be.mmv(F, Zf, self._arg(), v, ranges)
         if out is not None:
             out.copy_(res)
             return out
         return res
 
+
+class GaussianKernel(_RadialKernel):
+    """K(x, z) = exp(-|x - z|^2 / (2 sigma^2)); ``mmv`` is the fused scoring kernel."""
+    kernel_name = "gaussian"
+    kind = 0                    # ODX_KERNEL_GAUSS
+
+    def __init__(self, sigma, opt=None):
+        self.sigma = float(sigma)
+
     def __repr__(self):
         return "GaussianKernel(sigma=%g)" % self.sigma
+
+
+class MaternKernel(_RadialKernel):
+    """falkon's MaternKernel(sigma, nu) for nu = 3/2 and 5/2: with u = sqrt(2 nu) |x - z| / sigma,
+    K = (1 + u) exp(-u) and K = (1 + u + u^2 / 3) exp(-u).  The entries come from the Gaussian tiles' contraction X Z' with
+    another epilogue (odx_radial_*), so fit, fit_multi, fit_path, fit_cv, predict and predict_path run as for the Gaussian,
+    on stored blocks of every format.  nu = inf is the Gaussian itself (kind 0).  The estimators hand this object to the
+    backend where a Gaussian fit hands its sigma; it deliberately has no __float__, so that a route that was not taught the
+    kinds raises TypeError instead of evaluating a Gaussian."""
+    kernel_name = "matern"
+    _KINDS = {1.5: 1, 2.5: 2, float("inf"): 0}       # ODX_KERNEL_MATERN32 / _MATERN52 / _GAUSS
+
+    def __init__(self, sigma, nu, opt=None):
+        self.sigma = float(sigma)
+        self.nu = float(nu)
+        if self.nu == 0.5:
+            raise NotImplementedError(
+                "MaternKernel: nu = 1/2 is not offered: exp(-r / sigma) has an unbounded slope in d^2 at 0, where the f32 "
+                "evaluation of d^2 is off by up to 8e-4 for rows that are centres, so alpha misses the 1e-4 bar ten times over")
+        if self.nu not in self._KINDS:
+            raise ValueError("MaternKernel: nu must be 1.5, 2.5 or inf (the Gaussian), got %r" % (nu,))
+        self.kind = self._KINDS[self.nu]
+
+    def __repr__(self):
+        return "MaternKernel(sigma=%g, nu=%g)" % (self.sigma, self.nu)
+
+
+def _kernel_arg(kernel):
+    """The `sigma` argument an estimator hands down for its kernel: kernel.sigma for a Gaussian (any object with a sigma and
+    no kind, as ever), the kernel object itself for another kind."""
+    return kernel if getattr(kernel, "kind", 0) else kernel.sigma
+
+
+def _grid_refuse(kernel, what):
+    if getattr(kernel, "kind", 0):
+        raise NotImplementedError("%s: the sigma grid is Gaussian-only (its kernels take a width per block / column); got %r" % (what, kernel))
 
 
 class CVResult:
@@ -140,11 +187,11 @@ class _FalkonBase:
                              "binary classifier per fit); got Y with %d columns" % y.shape[1])
         if y.shape[1] == 1:
             yv = be.vec(y[:, 0])
-            alpha = falkon_fit(be, F, yv, Zf, self.kernel.sigma, float(self.penalty), int(self.maxiter),
+            alpha = falkon_fit(be, F, yv, Zf, _kernel_arg(self.kernel), float(self.penalty), int(self.maxiter),
                                self.options.solver_options()).reshape(-1, 1)
         else:
             # T label columns over the same rows and centres: one block, one preconditioner
-            alpha = falkon_fit_multi(be, F, be.vec(y), Zf, self.kernel.sigma, float(self.penalty), int(self.maxiter),
+            alpha = falkon_fit_multi(be, F, be.vec(y), Zf, _kernel_arg(self.kernel), float(self.penalty), int(self.maxiter),
                                      self.options.solver_options()).t().contiguous()          # (M, T), as upstream's alpha_
         if hasattr(be, "release_helper_streams"):
             be.release_helper_streams()          # (a chain of 4096 centres or more made helper streams: not left behind idle)
@@ -176,7 +223,7 @@ class _FalkonBase:
             raise ValueError("odx FALKON fits one right-hand side per model (the reference trains one "
                              "binary classifier per fit); got Y with %d columns" % y.shape[1])
         penalties = [float(p) for p in penalties]
-        alphas = falkon_fit_path(be, F, be.vec(y[:, 0]), Zf, self.kernel.sigma, penalties, int(self.maxiter),
+        alphas = falkon_fit_path(be, F, be.vec(y[:, 0]), Zf, _kernel_arg(self.kernel), penalties, int(self.maxiter),
                                  self.options.solver_options())
         if hasattr(be, "release_helper_streams"):
             be.release_helper_streams()
@@ -216,7 +263,7 @@ class _FalkonBase:
         if fold_of is None:
             fold_of = cv_folds(F.n, folds, seed)
         yv = be.vec(y[:, 0])
-        alphas, heldout = falkon_fit_cv(be, F, yv, Zf, self.kernel.sigma, penalties, fold_of, folds, int(self.maxiter),
+        alphas, heldout = falkon_fit_cv(be, F, yv, Zf, _kernel_arg(self.kernel), penalties, fold_of, folds, int(self.maxiter),
                                         self.options.solver_options(), refit=refit)
         if hasattr(be, "release_helper_streams"):
             be.release_helper_streams()
@@ -248,6 +295,7 @@ class _FalkonBase:
         and shared by all members (`ny_points_`); each member has its own GaussianKernel(sigma), `penalty` and `alpha_`.
         This estimator is the template and stays as it is."""
         import copy
+        _grid_refuse(self.kernel, "fit_grid")
         be = _backend.get_backend()
         F = be.features(X)
         if isinstance(self.center_selection, str):
@@ -349,6 +397,8 @@ def predict_path(estimators, X):
             raise ValueError("predict_path: the estimators must share one ny_points_ tensor (the members of a fit_path do)")
         if float(est.kernel.sigma) != float(first.kernel.sigma):
             raise ValueError("predict_path: the estimators must share sigma, got %g and %g" % (first.kernel.sigma, est.kernel.sigma))
+        if getattr(est.kernel, "kind", 0) != getattr(first.kernel, "kind", 0):
+            raise ValueError("predict_path: the estimators must share the kernel function, got %r and %r" % (first.kernel, est.kernel))
         if est.alpha_.dim() != 2 or tuple(est.alpha_.shape) != (first.ny_points_.shape[0], 1):
             raise ValueError("predict_path: every alpha_ must be (M, 1), got %s" % (tuple(est.alpha_.shape),))
     V = torch.cat([est.alpha_ for est in estimators], dim=1)
@@ -376,6 +426,7 @@ def predict_grid(estimators, X):
             raise ValueError("predict_grid: the estimators must share one ny_points_ tensor (the members of a fit_grid do)")
         if est.alpha_.dim() != 2 or tuple(est.alpha_.shape) != (first.ny_points_.shape[0], 1):
             raise ValueError("predict_grid: every alpha_ must be (M, 1), got %s" % (tuple(est.alpha_.shape),))
+        _grid_refuse(est.kernel, "predict_grid")
     sigmas = [float(est.kernel.sigma) for est in estimators]
     V = torch.cat([est.alpha_ for est in estimators], dim=1)
     be = _backend.get_backend()
@@ -431,7 +482,9 @@ def fit_batch(estimators, Xs, Ys, streams=None):
     groups = {}
     for i, est in enumerate(estimators):
         o = est.options.solver_options()
-        groups.setdefault((float(est.kernel.sigma), float(est.penalty), o.pc_epsilon), []).append(i)
+        # (another kernel kind: the object travels as sigma and precond_batched, which knows the Gaussian only, refuses it)
+        groups.setdefault((_kernel_arg(est.kernel) if getattr(est.kernel, "kind", 0) else float(est.kernel.sigma), float(est.penalty),
+                           o.pc_epsilon), []).append(i)
     from . import solver as _solver
     cur = torch.cuda.current_stream() if streams else None
     for (sigma, lam, eps), members in groups.items():
@@ -516,7 +569,7 @@ def fit_batch(estimators, Xs, Ys, streams=None):
                     if streams:
                         streams[i % len(streams)].wait_stream(cur)
                     with (torch.cuda.stream(streams[i % len(streams)]) if streams else _nullcontext()):
-                        alpha = falkon_fit(be, Fs[i], yvs[i], Zfs[i], est.kernel.sigma, float(est.penalty), int(est.maxiter),
+                        alpha = falkon_fit(be, Fs[i], yvs[i], Zfs[i], _kernel_arg(est.kernel), float(est.penalty), int(est.maxiter),
                                            opts[row], precond=P)
                 ny = Zfs[i].X.contiguous() if Zfs[i].X.stride(0) != Zfs[i].D else Zfs[i].X
                 est.alpha_, est.ny_points_ = alpha.reshape(-1, 1), ny
@@ -557,7 +610,7 @@ class BatchFit:
 
     def _key(self, est):
         o = est.options.solver_options()
-        return (float(est.kernel.sigma), float(est.penalty), o.pc_epsilon, int(est.maxiter),
+        return (_kernel_arg(est.kernel) if getattr(est.kernel, "kind", 0) else float(est.kernel.sigma), float(est.penalty), o.pc_epsilon, int(est.maxiter),
                 (o.cg_epsilon, o.cg_tolerance, o.cg_full_gradient_every, o.check_pivots))
 
     def add(self, estimators, Xs, Ys, expect_total=None, centres_cap=None):
@@ -717,5 +770,5 @@ class Falkon(_FalkonBase):
 
 
 # `from falkon import kernels` / `from falkon.options import *` surfaces
-kernels = types.SimpleNamespace(GaussianKernel=GaussianKernel)
+kernels = types.SimpleNamespace(GaussianKernel=GaussianKernel, MaternKernel=MaternKernel)
 options = types.SimpleNamespace(FalkonOptions=FalkonOptions)

@@ -23,6 +23,7 @@ Caches are rebuilt whenever models are (re)assigned — the demo's update_model 
 import torch
 
 from . import backend as _backend
+from .falkon import _kernel_arg
 
 
 def _fold_regressors(regressors, D, background):
@@ -83,7 +84,8 @@ class _OnlineHead:
                     ranges[i, 0], ranges[i, 1] = row, row + m.M
                     row += m.M
             longest = int((ranges[:, 1] - ranges[:, 0]).max()) if C else 0
-            self._cls_cache = (be.features(ny), V, ranges.to(dev), live[0].kernel.sigma, longest)
+            # (one fused launch for all classes is the Gaussian's: another kernel kind travels as the object and fails here)
+            self._cls_cache = (be.features(ny), V, ranges.to(dev), float(_kernel_arg(live[0].kernel)), longest)
         Zf, V, ranges, sigma, longest = self._cls_cache
         s = be.mmv(F, Zf, sigma, V, ranges, max_range=longest)
         for i, m in enumerate(self.classifiers):

@@ -15,7 +15,8 @@ _LIB_PATH = os.environ.get("ODX_LIB_PATH") or os.path.join(os.path.dirname(os.pa
 ODX_OK = 0
 KNM_F32, KNM_U24, KNM_BF16 = 0, 1, 2
 KNM_CODE = {"f32": KNM_F32, "u24": KNM_U24, "bf16": KNM_BF16}      # Knm.fmt -> the ODX_KNM_* code of include/odx.h
-STREAM_MAX_VECTORS = 16      # ODX_STREAM_MAX_VECTORS: vectors one odx_gauss_ktk_stream_h2n call serves from one build of K
+KERNEL_GAUSS, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 1, 2          # ODX_KERNEL_*: the radial kernels of the odx_radial_* entries
+STREAM_MAX_VECTORS = 16     # ODX_STREAM_MAX_VECTORS: vectors one odx_gauss_ktk_stream_h2n call serves from one build of K
 GRID_MAX_SIGMAS = 4         # ODX_GRID_MAX_SIGMAS: kernel widths one odx_gauss_knm_h2_store_sigmas call builds from one contraction
 GEMM_LOWER_ONLY, GEMM_A_UPPER, GEMM_B_UPPER, GEMM_A_LOWER, GEMM_B_LOWER, GEMM_STORE_T = 1, 2, 4, 8, 16, 32
 
@@ -68,6 +69,15 @@ SIGNATURES = {
     "odx_gauss_mmvn_h2_sigmas_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "odx_gauss_mmvn_h2_sigmas": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i64,
                                         _vp, _i64, _vp]),
+    "odx_radial_knm_h2_store": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _i32, _i32, _vp, _i64, _vp, _i64,
+                                       _vp, _vp, _vp, _i64, _vp]),
+    "odx_radial_mmv_h2": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _i32, _vp, _i64, _vp, _i32, _vp, _i64,
+                                 _vp, _i64, _vp]),
+    "odx_radial_mmvn_h2": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f64, _i32, _vp, _i64, _i32, _vp, _i64,
+                                  _vp, _i64, _vp]),
+    "odx_falkon_precond_radial_f64": (_i32, [_vp, _i64, _i64, _i32, _f64, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "odx_falkon_precond_path_radial_f64": (_i32, [_vp, _i64, _i64, _i32, _f64, _i32, _vp, _i32, _f64, _vp, _vp, _vp, _i64, _vp, _vp, _i64,
+                                                  _vp]),
     "odx_row_sqnorm_b16": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "odx_gauss_knm_b16_store_workspace_bytes": (_i64, [_i64, _i64]),
     "odx_gauss_knm_b16_store": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _f64, _i32, _vp, _i64, _vp, _i64, _vp, _vp,
@@ -217,6 +227,16 @@ SIGNATURES = {
     "odx_bias_act_nchw_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "odx_bias_act_nchw_16": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i64, _i32, _vp]),
 }
+
+
+def radial_of(sigma):
+    """(sigma, ODX_KERNEL_* kind) of the `sigma` argument of a backend wrapper that knows the radial kernels: a number is
+    the Gaussian's width, a kernel object (odx.MaternKernel) carries .sigma and .kind.  Wrappers that were not taught the
+    kind do float(sigma) on the object and fail there (it defines no __float__): nothing computes a Gaussian silently."""
+    kind = getattr(sigma, "kind", None)
+    if kind is None:
+        return float(sigma), KERNEL_GAUSS
+    return float(sigma.sigma), int(kind)
 
 
 def lib_path():

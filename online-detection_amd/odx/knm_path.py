@@ -477,9 +477,15 @@ class PathOps:
             raise ValueError("precond_path: out must be a contiguous %r f64 tensor" % (shape,))
         info = torch.zeros(L, dtype=torch.int32, device=self.device)
         ws = self._workspace(ws_key, self.lib.odx_falkon_precond_path_workspace_bytes(M, D, L))
-        hip.check(self.lib.odx_falkon_precond_path_f64(_p(Zf.X), Zf.ld, M, D, float(sigma), (ctypes.c_double * L)(*lams), L, float(eps),
-                                                       _p(mats[0]), _p(mats[1]), _p(mats[2]), ld, _p(info), _p(ws), ws.numel(),
-                                                       self._stream()), "odx_falkon_precond_path_f64")
+        sigma, kind = hip.radial_of(sigma)
+        if kind:             # a Matern kernel object: K_MM is that kernel's, the chain behind it the same
+            hip.check(self.lib.odx_falkon_precond_path_radial_f64(_p(Zf.X), Zf.ld, M, D, sigma, kind, (ctypes.c_double * L)(*lams), L,
+                                                                  float(eps), _p(mats[0]), _p(mats[1]), _p(mats[2]), ld, _p(info), _p(ws),
+                                                                  ws.numel(), self._stream()), "odx_falkon_precond_path_radial_f64")
+        else:
+            hip.check(self.lib.odx_falkon_precond_path_f64(_p(Zf.X), Zf.ld, M, D, sigma, (ctypes.c_double * L)(*lams), L, float(eps),
+                                                           _p(mats[0]), _p(mats[1]), _p(mats[2]), ld, _p(info), _p(ws), ws.numel(),
+                                                           self._stream()), "odx_falkon_precond_path_f64")
         members = []
         for l in range(L):
             P = Precond()

@@ -670,6 +670,7 @@ class OnlineRegionClassifierBase:
         if (dev == 'cuda' and self.num_classes > 2 and len(model) >= self.num_classes - 1
                 and all(m is not None and getattr(m, 'alpha_', None) is not None and hasattr(getattr(m, 'kernel', None), 'sigma')
                         for m in model[:self.num_classes - 1])
+                and not any(getattr(m.kernel, 'kind', 0) for m in model[:self.num_classes - 1])      # (the fused launch is Gaussian-only)
                 and len({float(m.kernel.sigma) for m in model[:self.num_classes - 1]}) == 1):
             from .heads import _OnlineHead
             fused = _OnlineHead(list(model[:self.num_classes - 1]), None, None)
