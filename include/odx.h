@@ -647,6 +647,28 @@ int odx_convert_f32_f64(const float* src, int64_t lds, double* dst, int64_t ldd,
 int odx_convert_f64_f32(const double* src, int64_t lds, float* dst, int64_t ldd, int64_t rows,
                         int64_t cols, odx_stream_t stream);
 
+/* ---------------------------------------------------------------- ridge leverage scores (odx/leverage.py)
+ * For a dictionary J of rows with weights c:  A = K_JJ + lam diag(c),  L = chol(A),  Li = L^-1 (odx_potrf_f64, odx_trtri_f64),
+ * q(x) = k_xJ A^-1 k_Jx = |Li k_Jx|^2  and the approximate leverage score is (1 - q(x)) / (lam n)  (radial kernels: k(x, x) = 1).
+ *
+ * odx_knm_rowquad_f64:  q[r] = sum_{j < M} ( sum_{c <= j} K[r, c] Li[j, c] )^2,  r < n.
+ * K: an f32-format K_nM block or a row sub-block of one, 16-byte aligned, ldk % 4 == 0, ldk >= M.  Li: lower triangular, f64,
+ * ldl >= M (an even ldl on a 16-byte boundary is read by 16-byte loads, anything else by 8-byte loads: the same bits).  Li[j, c > j],
+ * K[r, c >= M] and everything past row n are never used and may hold NaN; q[n ..] is never written.  n <= 0 or M < 0: nothing
+ * is written; M == 0: zeros.  ODX_ERR_INVALID for a misaligned K, ldk % 4 != 0 or a leading dimension below M.  Every product
+ * and sum is f64 (v_mfma_f64_16x16x4_f64; the f32 entries convert exactly); no scratch, no atomics, and q[r] does not depend,
+ * bit for bit, on n or on the other rows of the call: scores computed in row chunks are the unchunked ones.  The n x M product
+ * Li K' is never stored.
+ *
+ * odx_radial_kmm_f64: the lower triangle of the f64 kernel matrix (kind: ODX_KERNEL_*) of the f64 centres Zd (M x D, 16-byte
+ * aligned, ldz even; M < 65536), plus diag_scale * diag[j] on the diagonal (diag NULL: plus diag_scale).  zsq: M doubles, left
+ * holding the centres' squared norms.  The matrix the preconditioner chains factor, for any diagonal.  An unknown kind is
+ * ODX_ERR_INVALID. */
+int odx_knm_rowquad_f64(const float* K, int64_t ldk, int64_t n, int64_t M, const double* Li, int64_t ldl, double* q,
+                        odx_stream_t stream);
+int odx_radial_kmm_f64(const double* Zd, int64_t ldz, int64_t M, int D, double sigma, int kind, const double* diag,
+                       double diag_scale, double* Kmm, int64_t ldk, double* zsq, odx_stream_t stream);
+
 /* ---------------------------------------------------------------- A7: RLS box regressors
  * RegionRefinerTrainer.train / solve
  * (src/modules/region-refiner/region_refiner_trainer/train_region_refiner.py:25-119):

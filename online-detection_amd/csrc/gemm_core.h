@@ -116,6 +116,87 @@ __device__ __forceinline__ void gemm_store_operand(const u32x4 (&r)[NP], char* l
   }
 }
 
+// An f64 A tile staged from f32 rows (knm_rowquad_kernel: a K_nM block against an f64 factor): the k-tile's 16 elements are
+// 64 B of a row, four 16-B segments, so thread t fetches segments idx = t + 256 p, p < 2: row = idx >> 2, seg = idx & 3.
+// Rows >= nrows and k >= K read as zero — selected, never multiplied: those cells may hold NaN.  base is 16-byte aligned and
+// ld % 4 == 0, so a segment that starts below K ends inside its row.  CLEAN as in gemm_load_operand: the k-tile lies inside
+// [0, K), nothing is masked behind a load.
+template <bool CLEAN>
+__device__ __forceinline__ void gemm_load_operand_f32(f32x4 (&r)[2], const float* __restrict__ base, int64_t ld, int64_t row0,
+                                                      int64_t nrows, int64_t k0, int64_t K) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int idx = tid + GEMM_THREADS * p;
+    const int64_t gr = row0 + (idx >> 2);
+    const int64_t kk = k0 + (idx & 3) * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (CLEAN) {
+      if (gr < nrows) v = *reinterpret_cast<const f32x4*>(base + gr * ld + kk);
+    } else if (gr < nrows && kk < K) {
+      v = *reinterpret_cast<const f32x4*>(base + gr * ld + kk);
+      if (kk + 4 > K) {
+#pragma unroll
+        for (int q = 1; q < 4; ++q)
+          if (kk + q >= K) v[q] = 0.f;
+      }
+    }
+    r[p] = v;
+  }
+}
+
+// ... and its way into LDS: converted (exactly) to the f64 tile layout gemm_compute_ktile reads, 32 B per segment.
+__device__ __forceinline__ void gemm_store_operand_f32(const f32x4 (&r)[2], char* lds) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int idx = tid + GEMM_THREADS * p;
+    char* d = lds + (idx >> 2) * GEMM_LDS_ROW + (idx & 3) * 32;
+    *reinterpret_cast<f64x2*>(d) = f64x2{(double)r[p][0], (double)r[p][1]};
+    *reinterpret_cast<f64x2*>(d + 16) = f64x2{(double)r[p][2], (double)r[p][3]};
+  }
+}
+
+// An f64 B tile of a LOWER-TRIANGULAR operand (32 NP rows from row0, B[j, k > j] never used: those cells may hold NaN): thread t
+// fetches segments idx = t + 256 p of gemm_load_operand's layout; an element above the diagonal, in a row >= nrows or at k >= K is
+// zero by selection, and a segment wholly above the diagonal is not read.  VEC16: base 16-byte aligned and ld even (one
+// 16-byte load per segment); otherwise two 8-byte loads — the same values.  CLEAN: the k-tile lies inside [0, K) and wholly
+// below the diagonal of every row of the tile (k0 + BK <= row0): only the row bound is checked.
+template <bool VEC16, bool CLEAN, int NP>
+__device__ __forceinline__ void gemm_load_operand_lower(u32x4 (&r)[NP], const double* __restrict__ base, int64_t ld, int64_t row0,
+                                                        int64_t nrows, int64_t k0, int64_t K) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int idx = tid + GEMM_THREADS * p;
+    const int64_t gr = row0 + (idx >> 3);
+    const int64_t kk = k0 + (idx & 7) * 2;
+    f64x2 v = {0.0, 0.0};
+    if (CLEAN) {
+      if (gr < nrows) {
+        const double* src = base + gr * ld + kk;
+        if (VEC16) {
+          v = *reinterpret_cast<const f64x2*>(src);
+        } else {
+          v[0] = src[0];
+          v[1] = src[1];
+        }
+      }
+    } else if (gr < nrows && kk < K && kk <= gr) {
+      const double* src = base + gr * ld + kk;
+      const bool two = kk + 1 < K && kk + 1 <= gr;
+      if (VEC16) {
+        v = *reinterpret_cast<const f64x2*>(src);      // (kk + 1 < ld: ld is even and >= K)
+        if (!two) v[1] = 0.0;
+      } else {
+        v[0] = src[0];
+        if (two) v[1] = src[1];
+      }
+    }
+    r[p] = *reinterpret_cast<const u32x4*>(&v);
+  }
+}
+
 // MFMA work of one k-tile held in LDS.  wr / wc = wave row / column (0..1).
 template <int TN>
 __device__ __forceinline__ void gemm_compute_ktile(f32x16 (&acc)[2][TN], const char* ldsA, const char* ldsB,
