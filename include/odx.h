@@ -669,6 +669,32 @@ int odx_knm_rowquad_f64(const float* K, int64_t ldk, int64_t n, int64_t M, const
 int odx_radial_kmm_f64(const double* Zd, int64_t ldz, int64_t M, int D, double sigma, int kind, const double* diag,
                        double diag_scale, double* Kmm, int64_t ldk, double* zsq, odx_stream_t stream);
 
+/* ---------------------------------------------------------------- incremental FALKON (odx/incremental.py)
+ * With the centres fixed, FALKON's CG touches the rows only through K'K v and K'y: the M x M matrix G = K' diag(w) K, the vector
+ * b = K' (w o y) and n = sum w are all a fit needs, rows are added by accumulating into them (removed with w = -1, forgotten by
+ * beta < 1), and the CG's operator is A^-T [T^-T (G v / n) + lam v]: one read of G per iteration (odx_symvn_f64).
+ *
+ * odx_knm_gram_f64:  G[i, j] = beta G[i, j] + sum_{r < n} w[r] K[r, i] K[r, j]  (i, j < M),
+ *                    b[j]    = beta b[j]    + sum_{r < n} (w[r] y[r]) K[r, j]   (y and b: both given or both NULL).
+ * K: an f32-format K_nM block or a row sub-block of one, 16-byte aligned, ldk % 4 == 0, ldk >= M.  w, y: n doubles; w NULL means
+ * ones (the same bits as a vector of ones); negative weights are legal.  G: f64, 8-byte aligned, ldg >= M, SYMMETRIC on entry
+ * when beta != 0: the entries on and below the diagonal are the ones read, and both triangles are written with the same bits
+ * (G[i, j] is computed for i >= j and stored twice).  With beta == 0 G and b are never read and may hold NaN.  K[r, c >= M],
+ * G[., c >= M] and the rows of K, w, y past n are never read or written.  n <= 0: only the scale by beta (nothing for
+ * beta == 1); M <= 0: nothing.  ODX_ERR_INVALID for a misaligned K or G, ldk % 4 != 0, a leading dimension below M, or y
+ * without b.  Every product and sum is f64 on v_mfma_f64_16x16x4_f64 (the f32 entries convert exactly; w K is rounded once, as
+ * is w y); one workgroup owns a 128 x 64 output tile and walks the rows in ascending k-tiles of 32: no atomics, no workspace,
+ * the same call twice gives the same bits.  Two calls over row halves equal one call to rounding only.
+ *
+ * odx_symvn_f64:  Y[q] = alpha * G X[q] for q < nv, 1 <= nv <= 8, from ONE read of the full M x M f64 matrix G (16-byte
+ * aligned, ldg even, ldg >= M; G[., c >= M] is never read).  X / Y: nv f64 rows, ldx / ldy doubles apart; X rows 16-byte
+ * aligned, ldx even; the doubles Y spans must not overlap those X spans (ODX_ERR_INVALID).  Rows as dot products with odx_trmvn_f64's loads and reduction; sums in a fixed
+ * order, no scratch. */
+int odx_knm_gram_f64(const float* K, int64_t ldk, int64_t n, int64_t M, const double* w, const double* y, double beta,
+                     double* G, int64_t ldg, double* b, odx_stream_t stream);
+int odx_symvn_f64(const double* G, int64_t ldg, int64_t M, int nv, const double* X, int64_t ldx, double alpha, double* Y,
+                  int64_t ldy, odx_stream_t stream);
+
 /* ---------------------------------------------------------------- A7: RLS box regressors
  * RegionRefinerTrainer.train / solve
  * (src/modules/region-refiner/region_refiner_trainer/train_region_refiner.py:25-119):

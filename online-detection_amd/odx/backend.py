@@ -21,6 +21,7 @@ import torch
 
 from . import hip
 from .knm_path import PathOps, _p
+from .incremental_ops import IncrementalOps
 from .leverage_ops import LeverageOps
 
 
@@ -151,7 +152,7 @@ class KnmStream:
         self.K, self.fmt, self.lo = F.P, "stream", None
 
 
-class HipBackend(PathOps, LeverageOps):
+class HipBackend(PathOps, LeverageOps, IncrementalOps):
     name = "hip-gfx950"
     # The smallest number of columns for which a dense mmv (ranges None, gauss "h2") goes through odx_gauss_mmvn_h2: K(X, Z)
     # evaluated once per group of up to 8 columns instead of once per column, the same bits.  An attribute like

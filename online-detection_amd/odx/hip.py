@@ -174,6 +174,8 @@ SIGNATURES = {
     "odx_convert_f64_f32": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _vp]),
     "odx_knm_rowquad_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "odx_radial_kmm_f64": (_i32, [_vp, _i64, _i64, _i32, _f64, _i32, _vp, _f64, _vp, _i64, _vp, _vp]),
+    "odx_knm_gram_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _i64, _vp, _vp]),
+    "odx_symvn_f64": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _f64, _vp, _i64, _vp]),
     "odx_rls_gram_workspace_bytes": (_i64, [_i64, _i32]),
     "odx_rls_gram_f64": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "odx_rls_solve_workspace_bytes": (_i64, [_i32]),

@@ -20,9 +20,10 @@ class LeverageOps:
             return 0
         return int(self.lib.odx_gauss_h2_tile(n, M))
 
-    def knm_f32(self, F, Zf, kernel, route_rows=None):
+    def knm_f32(self, F, Zf, kernel, route_rows=None, out=None):
         """knm() in f32 format whatever the storage option says, built by the route a block of route_rows rows takes (direct
-        differences or a tile core: both are chosen by shape): a chunk of rows gets the entries the whole block has."""
+        differences or a tile core: both are chosen by shape): a chunk of rows gets the entries the whole block has.  out: knm's
+        (a preallocated buffer for the block)."""
         from . import options as _options
         saved = self.knm_storage
         self.knm_storage = "f32"
@@ -30,8 +31,8 @@ class LeverageOps:
             tile = self._tile_route(F.n if route_rows is None else int(route_rows), Zf.n, F.D, kernel)
             if tile:
                 with _options.override(h2_tile=tile):
-                    return self.knm(F, Zf, kernel)
-            return self.knm(F, Zf, kernel)
+                    return self.knm(F, Zf, kernel, out=out)
+            return self.knm(F, Zf, kernel, out=out)
         finally:
             self.knm_storage = saved
 

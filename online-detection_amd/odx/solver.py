@@ -363,6 +363,32 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
     return (alpha, K) if return_knm else alpha
 
 
+def falkon_fit_stats(be, G, b, n, P, lam, maxiter=20, opt=None):
+    """Fit one binary FALKON problem from its M x M statistics alone: G = K_nM' W K_nM ((M, ld) f64, both triangles),
+    b = K_nM' W y ((>= M,) f64) and n = sum w, for the centres and kernel the preconditioner P was built from.
+
+    The CG touches the rows only through K'K v and K'y, so with G in the place of K'K this is falkon_fit's schedule (_cg_run,
+    one state) with an exchange that is ONE be.symv over the 1 or 2 prepared vectors: M^2 doubles read per iteration whatever n
+    was.  The periodic full residual always folds (it rides in the same read of G).  Scores from the CG are not offered (there
+    are no rows).  The result is falkon_fit's alpha on all the rows the statistics hold, up to f64 rounding.  No host
+    synchronisation inside the loop.  Returns alpha (M,) f64."""
+    opt = opt or SolverOptions()
+    n = float(n)
+    if not n > 0.0:
+        raise ValueError("falkon_fit_stats: the statistics must hold a positive total weight, got n = %r" % (n,))
+    M = P.M
+    Mp = (M + 1) // 2 * 2                              # (rows 16-byte aligned for odd M too)
+    TT, CC = be.zeros(2 * Mp).view(2, Mp), be.zeros(2 * Mp).view(2, Mp)
+
+    def exchange(k, rows):
+        be.symv(G, TT[:k], out=CC[:k])
+
+    alpha = be.zeros(M)
+    cgs = [_cg_state(be, P, float(lam), b[:M] / n, M, _slots(TT, CC, M), True, alpha)]
+    _cg_run(be, cgs, exchange, n, maxiter, opt, True)
+    return alpha
+
+
 def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=None, allreduce=None, phase=None, knm_out=None,
                     knm_blocks=None):
     """Fit one binary FALKON problem at every penalty of `lams` from ONE K_nM block.
