@@ -361,6 +361,27 @@ int odx_knm_fwd_bwd2_q_cols_t(const void* K, int64_t ldk, const void* Klo, int64
                               const double* v, const double* v2, double* out, double* out2, double* t_out, void* workspace,
                               int64_t workspace_bytes, int64_t Mv, const int32_t* col_of, const int32_t* start,
                               const int32_t* pos, odx_stream_t stream);
+/* One forward and two backward products from one read of a compact-format block:
+ *   out1 = K' (K v),   out2 = K' s,   t_out (n f64 or NULL) = K v
+ * with s an n-long f64 vector the caller already holds.  The CG's fold step (odx.solver._cg_run) needs W p and W x_old; where
+ * it accumulates the scores S = sum_i a_i (K v_i) it holds K T^-1 A^-1 x_old = S already, so the second vector's forward
+ * product, its copy in LDS and its products with T's inverse are not formed again.  The kernel is the one-vector halves
+ * kernel with a second set of column sums fed by s[row]: s is read per row like w, rows [n, ..) of it are never read, and s
+ * is NOT added into K v (out1 and t_out are those of odx_knm_fwd_bwd_q_t(v, w = NULL) up to the order of the row sums).
+ * Widths: those of odx_knm_fwd_bwd2_q (ODX_ERR_UNSUPPORTED elsewhere: where odx_knm_fwd_bwd2_q_workspace_bytes is negative);
+ * both compact formats; pad columns [M, ld) must be finite, as the store leaves them.  Workspace: TWICE
+ * odx_knm_fwd_bwd2_q_workspace_bytes(n, M, fmt) bytes (a slab pair per half of a workgroup, where that kernel leaves one
+ * per workgroup).  v, s, out1, out2 must not be NULL (ODX_ERR_INVALID); alignment and workspace errors as
+ * odx_knm_fwd_bwd2_q.  n <= 0: out1 = out2 = 0.  Slab per half and vector, fixed-order reduce: bitwise reproducible, no
+ * atomics.  _cols_t: the same over a block of distinct columns (v, out1, out2 Mv long; s, t_out and the workspace are
+ * those of the M-column block), as odx_knm_fwd_bwd2_q_cols_t. */
+int odx_knm_fwd_bwd_q_rows_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                             const double* v, const double* s, double* out1, double* out2, double* t_out, void* workspace,
+                             int64_t workspace_bytes, odx_stream_t stream);
+int odx_knm_fwd_bwd_q_rows_cols_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                  const double* v, const double* s, double* out1, double* out2, double* t_out,
+                                  void* workspace, int64_t workspace_bytes, int64_t Mv, const int32_t* col_of,
+                                  const int32_t* start, const int32_t* pos, odx_stream_t stream);
 int odx_cols_fold_f64(const double* v, int64_t Mv, const int32_t* start, const int32_t* pos, int64_t M, double* out,
                       odx_stream_t stream);
 int odx_cols_expand_f64(const double* x, int64_t M, const int32_t* col_of, int64_t Mv, double* out, odx_stream_t stream);

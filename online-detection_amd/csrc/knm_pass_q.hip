@@ -260,14 +260,15 @@ __global__ __launch_bounds__(NT, WPE) void knm_passq_batched_kernel(PassBatchQ p
 // number of trips, all eight waves are resident by construction, and the spin is bounded.  Bitwise reproducible: a
 // half's column sums depend only on its own rows, the slab holds one vector per half, the fixed-order reduce adds
 // 2 x grid of them.
-template <int CH, int R, int FMT>
+template <int CH, int R, int FMT, bool ROWS = false>
 __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __restrict__ Khi, int64_t ldk,
                                                     const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n,
                                                     int64_t M, const double* __restrict__ v1,
                                                     const double* __restrict__ w, double* __restrict__ slab,
                                                     int64_t slab_ld, double* __restrict__ t_out, int wg, int nwg,
                                                     int64_t Mv = 0, const int* __restrict__ cstart = nullptr,
-                                                    const int* __restrict__ cpos = nullptr) {
+                                                    const int* __restrict__ cpos = nullptr,
+                                                    const double* __restrict__ srow = nullptr) {
   constexpr int NT = 256, CW = QCW;
   extern __shared__ __attribute__((aligned(16))) double vsq[];
   __shared__ double red[2][2][4][R];                 // [half][ping-pong][wave of the half][row]
@@ -285,10 +286,14 @@ __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __rest
   for (int i = tid; i < vcap; i += 512) vsq[i] = (v1 != nullptr && i < M) ? q_v_entry(v1, i, Mv, cstart, cpos) * vscale : 0.0;
   const int voff_hi = ht * (2 * CW), voff_lo = ht * CW;
   double acc[CH][CW];
+  double acs[ROWS ? CH : 1][CW];                     // ROWS: the column sums of K' s beside those of K' (K v)
 #pragma unroll
   for (int c = 0; c < CH; ++c)
 #pragma unroll
-    for (int e = 0; e < CW; ++e) acc[c][e] = 0.0;
+    for (int e = 0; e < CW; ++e) {
+      acc[c][e] = 0.0;
+      if (ROWS) acs[c][e] = 0.0;
+    }
   QChunk<FMT, CW> kr[R][CH];
   const int rowb_hi = (int)ldk * 2, rowb_lo = (int)ldlo;
   __amdgpu_buffer_rsrc_t rs_hi, rs_lo;
@@ -403,6 +408,10 @@ __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __rest
       if (row >= n) t[r] = 0.0;                      // a repeated row, not a zero one, was read for it
       else if (w != nullptr) t[r] += w[row];
     }
+    // ROWS: the row's entry of s, read as w is (uniform, outside the streaming part); never past row n - 1
+    double ts[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) ts[r] = (ROWS && blk * R + r < n) ? srow[blk * R + r] : 0.0;
     // ---- phase 2: the column sums, and the next block's loads chunk by chunk
     const bool more = k + 1 < mine;
     if (more) open_block(blk + step);
@@ -411,21 +420,35 @@ __device__ __forceinline__ void knm_passq_stag_body(const unsigned short* __rest
 #pragma unroll
       for (int r = 0; r < R; ++r)
 #pragma unroll
-        for (int e = 0; e < CW; ++e) acc[c][e] = fma(q_entry<FMT, CW>(kr[r][c], e), t[r], acc[c][e]);
+        for (int e = 0; e < CW; ++e) {
+          const double kd = q_entry<FMT, CW>(kr[r][c], e);
+          acc[c][e] = fma(kd, t[r], acc[c][e]);
+          if (ROWS) acs[c][e] = fma(kd, ts[r], acs[c][e]);
+        }
       // (unconditional: a branch around the loads makes every register of the block a loop-carried select — 120 register
       // copies per trip; after the last block the loads re-read it and nobody waits for them)
       load_block(c);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  double* my = slab + (2 * (int64_t)wg + h) * slab_ld;
+  // (ROWS: a half's slab is [sums of K'(K v) | sums of K' s], the layout the two-vector reducers read)
+  double* my = slab + (2 * (int64_t)wg + h) * slab_ld * (ROWS ? 2 : 1);
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     const int ch = ht + c * NT;
     if (ch < nchunk) {
+      if (ROWS) {
+        // (the scaled sums are formed here, chunk by chunk: hoisted above the branches they would all be live beside the
+        // unscaled ones, twice the two accumulator sets)
+#pragma unroll
+        for (int e = 0; e < CW; ++e) asm volatile("" : "+v"(acc[c][e]), "+v"(acs[c][e]));
+      }
 #pragma unroll
       for (int e = 0; e < CW; ++e)
-        if ((int64_t)ch * CW + e < slab_ld) my[(int64_t)ch * CW + e] = acc[c][e] * vscale;
+        if ((int64_t)ch * CW + e < slab_ld) {
+          my[(int64_t)ch * CW + e] = acc[c][e] * vscale;
+          if (ROWS) my[slab_ld + (int64_t)ch * CW + e] = acs[c][e] * vscale;
+        }
     }
   }
 }
@@ -448,6 +471,20 @@ __global__ __launch_bounds__(512, 2) void knm_passq_stag_batched_kernel(PassBatc
   if ((int)blockIdx.x >= pb.grid[b]) return;
   knm_passq_stag_body<CH, R, FMT>(pb.Khi[b], pb.ldk[b], pb.Klo[b], pb.ldlo[b], pb.n[b], pb.M[b], v + (int64_t)b * vstride, nullptr,
                                   slab + (int64_t)b * slab_stride, slab_ld, nullptr, (int)blockIdx.x, pb.grid[b]);
+}
+
+// ---------------------------------------------------------------- one forward, two backward products (the CG's fold step)
+// out1 = K'(K v), out2 = K' s with s an n-long vector the caller already holds (solver._cg_run: the accumulated row
+// products K T^-1 A^-1 x of the steps taken), t_out = K v: the halves kernel above with a second set of column sums fed by
+// s[row] — phase 1, the rendezvous and the loads are the one-vector kernel's, ONE copy of v in LDS.  A half's slab is
+// [K'(K v) | K' s].
+template <int CH, int R, int FMT>
+__global__ __launch_bounds__(512, 2) void knm_passq_rows_kernel(
+    const unsigned short* __restrict__ Khi, int64_t ldk, const unsigned char* __restrict__ Klo, int64_t ldlo, int64_t n, int64_t M,
+    const double* __restrict__ v1, const double* __restrict__ srow, double* __restrict__ slab, int64_t slab_ld,
+    double* __restrict__ t_out, int64_t Mv, const int* __restrict__ cstart, const int* __restrict__ cpos) {
+  knm_passq_stag_body<CH, R, FMT, true>(Khi, ldk, Klo, ldlo, n, M, v1, nullptr, slab, slab_ld, t_out, (int)blockIdx.x,
+                                            (int)gridDim.x, Mv, cstart, cpos, srow);
 }
 
 struct QCfg {
@@ -770,6 +807,86 @@ extern "C" int odx_knm_fwd_bwd2_q_t(const void* K, int64_t ldk, const void* Klo,
   return knm_fwd_bwd2_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, v2, out, out2, t_out, workspace, workspace_bytes, stream);
 }
 
+// ---- one forward, two backward products: out1 = K'(K v), out2 = K' s, t_out = K v (knm_passq_rows_kernel)
+struct QRowsCfg {
+  int ch, r;      // chunks per thread of a half, rows per block
+};
+
+// The widths of the two-vector rule (pick_qcfg, nv = 2), so that a caller that may fold with two vectors may fold with this.
+// Two accumulator sets beside the block: 8 chunks per thread leave room for two-row blocks, 10 for one row (two rows, or
+// halves of 512 threads x 5 chunks x 2 rows, spill).  Alone at n = 1e6, 24-bit format (profiles/fold_rows.md): M = 1e4:
+// 256 x 10 x 1 row 5.37 ms, halves of 512 threads x 5 x 1 row 5.69 ms (two vectors: 7.51); M = 8000: 256 x 8 x 2 rows
+// 4.07 ms, 256 x 8 x 1 row 4.47 ms, 512 x 4 x 1 row 4.93 ms (two vectors: 6.86).  The losers are not built.
+static bool pick_qrows_cfg(int64_t M, int fmt, QRowsCfg* cfg) {
+  QCfg two;
+  if (!pick_qcfg(M, 2, fmt, &two)) return false;
+  const int64_t chunks = (M + 3) / 4;
+  if (chunks <= 2048) *cfg = {8, 2};
+  else *cfg = {10, 1};
+  return true;
+}
+
+static int qrows_grid(const QRowsCfg& cfg, int64_t n) {
+  const int64_t pairs = ceil_div(ceil_div(n, cfg.r), 2);      // one row block per half and trip
+  const int64_t g = std::min<int64_t>(pass_cus(), pairs);
+  return (int)(g < 1 ? 1 : g);
+}
+
+template <int FMT>
+static int dispatch_passq_rows(const QRowsCfg& cfg, const QBlock& b, int grid, hipStream_t s, const double* v, const double* srow,
+                               double* slab, int64_t slab_ld, double* t_out, const QCols& cm) {
+#define ODX_QR(CH_, R_)                                                                                                          \
+  if (cfg.ch == CH_ && cfg.r == R_)                                                                                              \
+  return q_launch(knm_passq_rows_kernel<CH_, R_, FMT>, dim3(grid), 512, (size_t)(CH_ * 256 * 4) * sizeof(double), s, b.hi, b.ldk,     \
+                  b.lo, b.ldlo, b.n, b.M, v, srow, slab, slab_ld, t_out, cm.Mv, cm.start, cm.pos)
+  ODX_QR(8, 2);
+  ODX_QR(10, 1);
+#undef ODX_QR
+  set_error("odx_knm_fwd_bwd_q_rows: no kernel for this configuration");
+  return ODX_ERR_UNSUPPORTED;
+}
+
+static int knm_fwd_bwd_q_rows_impl(const char* who, const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n,
+                                   int64_t M, const double* v, const double* srow, double* out, double* out2, double* t_out,
+                                   void* workspace, int64_t workspace_bytes, odx_stream_t stream, const QCols& cm = QCols()) {
+  ODX_REQUIRE(M > 0 && out && out2, "%s: M <= 0 or null out", who);
+  hipStream_t s = as_stream(stream);
+  if (n <= 0) {
+    ODX_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)(cm.on() ? cm.Mv : M) * sizeof(double), s));
+    ODX_CHECK_HIP(hipMemsetAsync(out2, 0, (size_t)(cm.on() ? cm.Mv : M) * sizeof(double), s));
+    return ODX_OK;
+  }
+  ODX_REQUIRE(v && srow, "%s: null v or s", who);
+  ODX_PROPAGATE(check_q_block(who, K, ldk, Klo, ldlo, fmt, M));
+  QRowsCfg cfg;
+  if (!pick_qrows_cfg(M, fmt, &cfg)) {
+    set_error("%s: M = %lld is outside the two-vector configurations", who, (long long)M);
+    return ODX_ERR_UNSUPPORTED;
+  }
+  // (the kernel's v is zero-filled up to the ch x 256 chunks a half walks: they must cover the row)
+  ODX_REQUIRE((int64_t)cfg.ch * 256 * 4 >= M, "%s: configuration narrower than the block", who);
+  const int grid = qrows_grid(cfg, n);
+  const int64_t slab_ld = round_up(M, 4);
+  // one [K'(K v) | K' s] per half: twice the slabs of the two-vector kernel's one workgroup per CU, hence the entry's
+  // workspace of twice odx_knm_fwd_bwd2_q_workspace_bytes
+  const int nslab = 2 * grid;
+  ODX_PROPAGATE(require_workspace(who, workspace, workspace_bytes, 2 * (int64_t)nslab * slab_ld * (int64_t)sizeof(double)));
+  double* slab = static_cast<double*>(workspace);
+  ODX_PROPAGATE(q_dispatch(q_block(K, ldk, Klo, ldlo, fmt, n, M), [&](auto f, const QBlock& b) {
+    return dispatch_passq_rows<decltype(f)::value>(cfg, b, grid, s, v, srow, slab, slab_ld, t_out, cm);
+  }));
+  ODX_CHECK_LAUNCH(who);
+  if (cm.on()) return slab_reduce_cols_f64(slab, slab_ld, nslab, 2, M, cm.Mv, cm.col_of, out, out2, s);
+  return slab_reduce2_f64(slab, slab_ld, nslab, M, out, out2, s);
+}
+
+extern "C" int odx_knm_fwd_bwd_q_rows_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                        const double* v, const double* s, double* out1, double* out2, double* t_out, void* workspace,
+                                        int64_t workspace_bytes, odx_stream_t stream) {
+  return knm_fwd_bwd_q_rows_impl("odx_knm_fwd_bwd_q_rows_t", K, ldk, Klo, ldlo, fmt, n, M, v, s, out1, out2, t_out, workspace,
+                                 workspace_bytes, stream);
+}
+
 // The same two passes over a block that holds the DISTINCT columns of an Mv-long centre list (see include/odx.h): v / out are
 // Mv long, the block, its slabs and the workspace are those of its M columns.
 extern "C" int odx_knm_fwd_bwd_q_cols_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
@@ -789,4 +906,14 @@ extern "C" int odx_knm_fwd_bwd2_q_cols_t(const void* K, int64_t ldk, const void*
   const QCols cm = {Mv, col_of, start, pos};
   ODX_PROPAGATE(check_q_cols("odx_knm_fwd_bwd2_q_cols_t", cm, M));
   return knm_fwd_bwd2_q_impl(K, ldk, Klo, ldlo, fmt, n, M, v, v2, out, out2, t_out, workspace, workspace_bytes, stream, cm);
+}
+
+extern "C" int odx_knm_fwd_bwd_q_rows_cols_t(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                                             const double* v, const double* s, double* out1, double* out2, double* t_out,
+                                             void* workspace, int64_t workspace_bytes, int64_t Mv, const int32_t* col_of,
+                                             const int32_t* start, const int32_t* pos, odx_stream_t stream) {
+  const QCols cm = {Mv, col_of, start, pos};
+  ODX_PROPAGATE(check_q_cols("odx_knm_fwd_bwd_q_rows_cols_t", cm, M));
+  return knm_fwd_bwd_q_rows_impl("odx_knm_fwd_bwd_q_rows_cols_t", K, ldk, Klo, ldlo, fmt, n, M, v, s, out1, out2, t_out, workspace,
+                                 workspace_bytes, stream, cm);
 }

@@ -116,6 +116,9 @@ SIGNATURES = {
     "odx_knm_fwd_bwd_q_cols_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "odx_knm_fwd_bwd2_q_cols_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
                                          _vp]),
+    "odx_knm_fwd_bwd_q_rows_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "odx_knm_fwd_bwd_q_rows_cols_t": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
+                                             _vp, _vp]),
     "odx_cols_fold_f64": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "odx_cols_expand_f64": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "odx_cg_scores_axpy_f64": (_i32, [_vp, _vp, _vp, _i64, _vp]),

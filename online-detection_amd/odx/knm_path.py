@@ -4,7 +4,8 @@ that share one block are driven by: a lambda path (solver.falkon_fit_path: L pen
 
 ``PathOps`` is mixed into ``backend.HipBackend``.  It holds every wrapper of a pass over a stored block or a streamed shard,
 all HIP through libodx: one vector (``ktk``: odx_knm_fwd_bwd[_q]_t, odx_gauss_ktk_stream_h2), two (``ktk2``:
-odx_knm_fwd_bwd2[_q]_t), several from one read of the block (``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, ktk2 and
+odx_knm_fwd_bwd2[_q]_t), one vector and an n-long row vector (``ktk_rows``: odx_knm_fwd_bwd_q_rows[_cols]_t, the CG's fold step
+over accumulated scores), several from one read of the block (``ktkn``: odx_knm_fwd_bwdn_q for groups of 3 .. 8 vectors, ktk2 and
 ktk for the rest; where the one-read pass does not exist — above M = 5084 — groups of up to 8 from TWO reads, ``kvn``:
 odx_knm_fwdn_q, then odx_knm_bwdn_q, when ``wide_pass_min`` is set; on a streamed shard odx_gauss_ktk_stream_h2n, up to 16
 vectors from one BUILD of K), the right-hand sides of several label columns from one read of the block (``ktwn``:
@@ -188,6 +189,38 @@ class PathOps:
         else:
             ws = self._pass_ws("ktk", "odx_knm_fwd_bwd2", K)
             self._call("odx_knm_fwd_bwd2_t", *_fblock(K), K.n, K.M, *vecs, _p(ws), ws.numel())
+        return out1, out2
+
+    # Whether the CG's fold step takes K' S from the accumulated row products (ktk_rows) where it can.  An attribute, not an
+    # option: A/B runs and tests switch it on the backend.  profiles/fold_rows.md has the figures.
+    fold_rows = True
+
+    def can_ktk_rows(self, K):
+        """Whether ktk_rows serves this block: a compact stored block at the widths of the two-vector pass (a block of distinct
+        columns answers as the full block of its centre list would, as can_ktk2 does), and the route is on (fold_rows)."""
+        return bool(self.fold_rows and K.fmt != "stream" and _compact(K) and self.can_ktk2(K))
+
+    def ktk_rows(self, K, v, s, out1=None, out2=None, t_out=None):
+        """out1 = K' (K v), out2 = K' s over this shard from ONE read of K, s an (n,) f64 vector of row values the caller holds
+        (odx_knm_fwd_bwd_q_rows[_cols]_t): the fold step of the CG with s = the accumulated row products K T^-1 A^-1 x.  s is
+        not added into K v.  t_out: optional (n,) f64 that receives K v."""
+        if not _compact(K):
+            raise ValueError("ktk_rows: compact stored blocks only (u24 / bf16), got %r" % (K.fmt,))
+        if s is None or s.dtype != torch.float64 or s.numel() != K.n or not s.is_contiguous():
+            raise ValueError("ktk_rows: s must be a contiguous f64 vector of the block's %d rows" % K.n)
+        if t_out is not None:
+            self._check_t_out(K, v, t_out)
+        if out1 is None:
+            out1 = torch.empty(_vlen(K), dtype=torch.float64, device=self.device)
+        if out2 is None:
+            out2 = torch.empty(_vlen(K), dtype=torch.float64, device=self.device)
+        # (a slab pair per half of a workgroup: twice the two-vector pass's workspace, include/odx.h)
+        ws = self._workspace("ktk", 2 * self._pass_bytes("odx_knm_fwd_bwd2_q", max(K.n, 1), K.M, hip.KNM_CODE[K.fmt]))
+        vecs = (_p(v), _p(s), _p(out1), _p(out2), _p(t_out))
+        if _mapped(K) is not None:
+            self._call("odx_knm_fwd_bwd_q_rows_cols_t", *_qblock(K), K.n, K.M, *vecs, _p(ws), ws.numel(), *_cols(K, self.device))
+        else:
+            self._call("odx_knm_fwd_bwd_q_rows_t", *_qblock(K), K.n, K.M, *vecs, _p(ws), ws.numel())
         return out1, out2
 
     # ------------------------------------------------------------------ several vectors

@@ -140,11 +140,15 @@ def _cg_state(be, P, lam, b0, M, io, fold, alpha=None, tk=None, scores=None):
     return c
 
 
-def _pass(be, ph, K, T, C, M, t_out=None):
+def _pass(be, ph, K, T, C, M, t_out=None, s=None):
     """C[j, :M] = K' (K T[j, :M]) for the one or two rows of T from one read of K.  t_out (receives K T[0, :M] over this
-    rank's rows) is passed on only when set: backends without score accumulation do not know the keyword."""
+    rank's rows) is passed on only when set: backends without score accumulation do not know the keyword.  s (the fold step
+    over accumulated scores, see _cg_run): this rank's rows of K T^-1 A^-1 x; then C[1, :M] = K' s and T[1] is not read."""
     kw = {} if t_out is None else {"t_out": t_out}
-    if T.shape[0] == 2:
+    if s is not None:
+        with ph("ktk2"):                                 # (the fold's one read of K, whichever kernel makes it)
+            be.ktk_rows(K, T[0, :M], s, out1=C[0, :M], out2=C[1, :M], **kw)
+    elif T.shape[0] == 2:
         with ph("ktk2"):
             be.ktk2(K, T[0, :M], T[1, :M], out1=C[0, :M], out2=C[1, :M], **kw)
     else:
@@ -159,7 +163,12 @@ def _sum(ar, C):
         C.copy_(r)
 
 
-def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared=None):
+def _fold_rows(be, Ks):
+    """Whether the fold step of fits that accumulate scores over the blocks Ks takes K' S from those scores (see _cg_run)."""
+    return bool(hasattr(be, "ktk_rows") and Ks and all(be.can_ktk_rows(K) for K in Ks))
+
+
+def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared=None, fold_rows=False):
     """falkon's preconditioned CG schedule, for the states `cgs` this rank holds (none on a rank that only passes over its
     rows), all advancing in lock step.  Returns with every c.alpha = T^-1 A^-1 x.
 
@@ -171,6 +180,16 @@ def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared=None):
     x_new = x_old + a p, so W x_new = W x_old + a W p, and W x_old comes out of the SAME read of K_nM as this step's W p (a
     two-vector exchange).  Same value up to f64 rounding, and still computed from fresh products, so it keeps removing the
     recursive drift the recomputation exists for.  No host synchronisation: step sizes and stop flags stay on the device.
+
+    fold_rows: the driver's statement that every state accumulates scores (the caller's scores_out, or a buffer the driver
+    made for the purpose: the route does not depend on whether scores were asked for) and that its exchange takes a third argument,
+    exchange(2, rows, True): the fold step's second product from the scores.  A state's scores are S = sum_i a_i (K v_i) over
+    the steps its iterate received (cg_scores_axpy and cg_step drop the same steps), so S = K T^-1 A^-1 x_old over this
+    rank's rows: the forward product of the fold's second vector is in memory, and K'K T^-1 A^-1 x_old = K' S.  The exchange
+    then leaves K' S (summed over the shards) where it would have left the second vector's product; only A^-1 x_old is
+    still formed, for the lam A^-1 x term.  S is a sum of products made fresh from K, not a recursively updated quantity, so
+    the residual is still rebuilt from fresh products; the value differs from the two-vector form's by f64 rounding of
+    sum_i a_i (K v_i) against K (sum_i a_i v_i).  This iteration's cg_scores_axpy runs behind the pass: it reads S_old.
 
     shared: the _Rows whose matrices the vectors of ALL states are rows of, state l row l — the driver's statement that they
     share one P and lam and that the backend has trmvn: every triangular product of the L states is then one be.trmvn.
@@ -191,26 +210,34 @@ def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared=None):
             be.trmvn(P, "LTi", sh.recv[j * L:(j + 1) * L], alpha=1.0 / n, beta=lam, Z=sh.v[j], out=sh.U)    # T^-T cc / n + lam v
             be.trmvn(P, "LAi", sh.U, out=getattr(sh, out))                                     # A^-T u
 
-    def W1(*pairs, rows=False):
+    def W1(*pairs, rows=False, srows=False):
         """c.<out> = W c.<s> for every (s, out) of pairs and every state c, W = A^-T [ T^-T K'K (T^-1 A^-1 .) / n + lam A^-1 . ],
-        from one exchange.  Vector kind outer, state inner."""
+        from one exchange.  Vector kind outer, state inner.  srows (fold_rows): the second vector is the iterate, whose
+        K T^-1 A^-1 x the exchange reads from the state's scores — no product with T's inverse, nothing to send."""
         k = len(pairs)
         for j, (s, _) in enumerate(pairs):
             for c in cgs:
                 be.trmv(c.P, "LAit", getattr(c, s), out=c.v[j])        # A^-1 s
-                be.trmv(c.P, "LTit", c.v[j], out=c.io[k - 1][j][0])    # T^-1 A^-1 s
-        exchange(k, rows)                                              # K' K of each, summed over shards
+                if not (srows and j == 1):
+                    be.trmv(c.P, "LTit", c.v[j], out=c.io[k - 1][j][0])    # T^-1 A^-1 s
+        if srows:
+            exchange(k, rows, True)
+        else:
+            exchange(k, rows)                                          # K' K of each, summed over shards
         for j, (_, out) in enumerate(pairs):
             for c in cgs:
                 u = be.trmv(c.P, "LTi", c.io[k - 1][j][1], alpha=1.0 / n, beta=c.lam, z=c.v[j])    # T^-T cc / n + lam v
                 be.trmv(c.P, "LAi", u, out=getattr(c, out))            # A^-T u
 
     W = W1 if sh is None else Wn
+    fold_rows = bool(fold_rows and sh is None and all(c.scores is not None for c in cgs))
     tol = opt.cg_tolerance ** 2
     for it in range(maxiter):
         full = (it + 1) % opt.cg_full_gradient_every == 0
         fold = can_fold and full and it != maxiter - 1
-        if fold:
+        if fold and fold_rows:
+            W(("Pv", "AP"), ("X", "AX"), rows=acc, srows=True)         # W p and W x_old, the latter from the scores
+        elif fold:
             W(("Pv", "AP"), ("X", "AX"), rows=acc)                     # W p and W x_old
         else:
             W(("Pv", "AP"), rows=acc)
@@ -343,13 +370,21 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
             _check_pivots(be, P)
         return (alpha, K) if return_knm else alpha
 
+    # the fold step over the summed row products (_cg_run, fold_rows) is this fit's fold wherever the rank could sum them,
+    # asked for or not: the sum is then kept in a buffer of the fit's own, so that scores_out changes nothing in alpha
+    fold_rows = bool(can_fold and (shard is None or owner is None) and scores_from_cg(be, K) and _fold_rows(be, [K]))
+    if fold_rows and not acc:
+        acc, scores_out = True, be.zeros(K.n)
+        tk = torch.empty_like(scores_out)
+
     k, Mp = 2 if can_fold else 1, (M + 1) // 2 * 2     # (rows 16-byte aligned for odd M too)
     TT, CC = be.zeros(k * Mp).view(k, Mp), be.zeros(k * Mp).view(k, Mp)
 
-    def exchange(k, rows):
-        """The owner's vector(s) to every rank, every rank's pass over its rows, the partials summed."""
-        bcast(TT if k == 2 else TT[0, :M])
-        _pass(be, ph, K, TT[:k], CC[:k], M, tk if rows else None)
+    def exchange(k, rows, srows=False):
+        """The owner's vector(s) to every rank, every rank's pass over its rows, the partials summed.  srows: the second
+        product is K' of this rank's rows of the scores (every rank holds the state then: nothing to send for it)."""
+        bcast(TT if k == 2 and not srows else TT[0, :M])
+        _pass(be, ph, K, TT[:k], CC[:k], M, tk if rows else None, scores_out if srows else None)
         _sum(ar, CC if k == 2 else CC[0, :M])
 
     alpha = be.zeros(M)
@@ -358,7 +393,7 @@ def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, all
         if precond_ready is not None:
             precond_ready()
         cgs.append(_cg_state(be, P, lam, b0, M, _slots(TT, CC, M), can_fold, alpha, tk, scores_out if acc else None))
-    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold)
+    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, fold_rows=fold_rows)
     bcast(alpha)
     return (alpha, K) if return_knm else alpha
 
@@ -766,19 +801,26 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
             S.zero_()
         tks = [torch.empty_like(S) for S in scores_out]      # K v of problem b's current direction, this rank's rows
     can_fold = B > 0 and _can_fold(be, Ks[0], M, int(n) // world)
+    # the fold step over the summed row products, asked for or not (see falkon_fit)
+    fold_rows = bool(can_fold and world == 1 and all(scores_from_cg(be, K) for K in Ks) and _fold_rows(be, Ks))
+    if fold_rows and not acc:
+        acc, scores_out = True, [be.zeros(K.n) for K in Ks]
+        tks = [torch.empty_like(S) for S in scores_out]
     if can_fold:
         Tall.append(be.zeros(world * 2 * Mp).view(world, 2 * Mp))
         CC.append(be.zeros(world * 2 * Mp).view(world, 2 * Mp))
     kmax = len(Tall)
     mine, got = be.zeros(kmax * Mp).view(kmax, Mp), be.zeros(kmax * Mp).view(kmax, Mp)    # what this rank sends / is handed
 
-    def exchange(k, rows):
-        """One all-gather of every owner's vector(s), B passes over this rank's rows, one reduce-scatter of the partials."""
+    def exchange(k, rows, srows=False):
+        """One all-gather of every owner's vector(s), B passes over this rank's rows, one reduce-scatter of the partials.
+        srows (one rank, scores accumulated): problem b's second product is K' of its scores."""
         Ta, Ca = Tall[k - 1], CC[k - 1]
         shard.gather_rows(mine[:k].view(-1), Ta)
         for b in range(B):
             o = owners[b]
-            _pass(be, ph, Ks[b], Ta[o].view(k, Mp), Ca[o].view(k, Mp), M, tks[b] if rows else None)
+            _pass(be, ph, Ks[b], Ta[o].view(k, Mp), Ca[o].view(k, Mp), M, tks[b] if rows else None,
+                  scores_out[b] if srows else None)
         shard.reduce_scatter_rows(Ca, got[:k].view(-1))
 
     shard.reduce_scatter_rows(CC[0], got[0])         # K' (y / n) of every problem: each owner gets the sum of its row
@@ -790,6 +832,6 @@ def falkon_fit_lockstep(be, F, ys, Zfs, sigma, lam, maxiter=20, opt=None, n_tota
         b = owners.index(rank)
         cgs.append(_cg_state(be, P, lam, got[0, :M], M, _slots(mine, got, M), can_fold, abuf[:M],
                              tks[b] if acc else None, scores_out[b] if acc else None))
-    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold)
+    _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, fold_rows=fold_rows)
     shard.gather_rows(abuf, Tall[0])
     return [Tall[0][owners[b], :M].clone() for b in range(B)]
