@@ -716,6 +716,31 @@ int odx_knm_gram_f64(const float* K, int64_t ldk, int64_t n, int64_t M, const do
 int odx_symvn_f64(const double* G, int64_t ldg, int64_t M, int nv, const double* X, int64_t ldx, double alpha, double* Y,
                   int64_t ldy, odx_stream_t stream);
 
+/* ---------------------------------------------------------------- logistic FALKON (odx/logistic.py)
+ * Newton steps on the weighted logistic loss over the rows of one stored K_nM block, each solved by falkon's CG: the Hessian
+ * product is K' (d o (K v)) with d the loss's second derivatives at the current scores, the gradient K' g.
+ *
+ * odx_knm_fwd_bwd_rw:  out[j] = sum_{r < n} K[r, j] d[r] t[r],  t[r] = sum_j K[r, j] v[j],  from ONE read of an f32-format
+ * block (K as odx_knm_fwd_bwd takes it: 16-byte aligned, ldk % 4 == 0, ldk >= roundup(M, 4), columns [M, roundup(M, 4)) zero;
+ * every (n, M, ldk) that entry serves).  v: M doubles.  d: n doubles or NULL — NULL means ones, and gives the same bits as a
+ * vector of ones; a weight of exactly 0 removes its row; negative weights are legal.  t_out (n doubles or NULL) receives t as
+ * reduced, BEFORE the weight; `out` is the same bits with or without it.  Workspace: exactly
+ * odx_knm_fwd_bwd_workspace_bytes(n, M), that entry's slabs.  The grid covers the whole device: odx_set_pass_reserved_cus is
+ * not honoured.  odx_knm_fwd_bwd's persistent row blocks; a row's weight is
+ * loaded ahead of the row dots and multiplied once into the reduced dot.  f64 sums in a fixed order, no atomics: the same call
+ * twice gives the same bits.  n <= 0: out = 0.  ODX_ERR_UNSUPPORTED above M = 20000, ODX_ERR_WORKSPACE, ODX_ERR_INVALID for a
+ * null K, v or out and a misaligned K.
+ *
+ * odx_logistic_rows_f64:  for r < n, with z = y[r] t[r], s = 1 / (1 + exp(z)) and c = 1 for y[r] > 0, neg_weight otherwise,
+ *     g[r] = -c y[r] s,   w[r] = c s (1 - s),   l[r] = c (max(-z, 0) + log1p(exp(-|z|)))
+ * the first and second derivative in t and the value of c log(1 + exp(-y t)).  Any of g, w, l may be NULL.  s and 1 - s are
+ * quotients over 1 + exp(-|z|), never a difference; every output is finite for every finite t.  y outside {-1, +1} is the
+ * caller's error and is not looked for.  neg_weight must be positive and finite (ODX_ERR_INVALID). */
+int odx_knm_fwd_bwd_rw(const float* K, int64_t ldk, int64_t n, int64_t M, const double* v, const double* d, double* out,
+                       double* t_out, void* workspace, int64_t workspace_bytes, odx_stream_t stream);
+int odx_logistic_rows_f64(const double* t, const double* y, int64_t n, double neg_weight, double* g, double* w, double* l,
+                          odx_stream_t stream);
+
 /* ---------------------------------------------------------------- A7: RLS box regressors
  * RegionRefinerTrainer.train / solve
  * (src/modules/region-refiner/region_refiner_trainer/train_region_refiner.py:25-119):

@@ -7,6 +7,8 @@ from .solver import SolverOptions, cv_folds, falkon_fit, falkon_fit_cv, falkon_f
 from .falkon import Falkon, FalkonOptions, GaussianKernel, InCoreFalkon, MaternKernel, predict_grid, predict_path  # noqa: F401
 from .leverage import LeverageSelector, leverage_scores  # noqa: F401
 from .incremental import IncrementalFalkon  # noqa: F401
+from .logistic import LogisticFalkon, LogisticLoss, falkon_fit_logistic  # noqa: F401
 
 __all__ = ["hip", "options", "get_backend", "set_backend", "SolverOptions", "falkon_fit", "falkon_fit_lockstep", "falkon_fit_path", "falkon_fit_multi", "falkon_fit_grid", "falkon_fit_cv", "falkon_fit_stats", "cv_folds", "Falkon", "InCoreFalkon",
-           "GaussianKernel", "MaternKernel", "FalkonOptions", "predict_path", "predict_grid", "leverage_scores", "LeverageSelector", "IncrementalFalkon"]
+           "GaussianKernel", "MaternKernel", "FalkonOptions", "predict_path", "predict_grid", "leverage_scores", "LeverageSelector", "IncrementalFalkon", "LogisticFalkon", "LogisticLoss",
+           "falkon_fit_logistic"]

@@ -23,6 +23,7 @@ from . import hip
 from .knm_path import PathOps, _p
 from .incremental_ops import IncrementalOps
 from .leverage_ops import LeverageOps
+from .logistic_ops import LogisticOps
 
 
 B16_DTYPES = (torch.bfloat16, torch.float16)
@@ -152,7 +153,7 @@ class KnmStream:
         self.K, self.fmt, self.lo = F.P, "stream", None
 
 
-class HipBackend(PathOps, LeverageOps, IncrementalOps):
+class HipBackend(PathOps, LeverageOps, IncrementalOps, LogisticOps):
     name = "hip-gfx950"
     # The smallest number of columns for which a dense mmv (ranges None, gauss "h2") goes through odx_gauss_mmvn_h2: K(X, Z)
     # evaluated once per group of up to 8 columns instead of once per column, the same bits.  An attribute like
