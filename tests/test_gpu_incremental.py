@@ -70,8 +70,21 @@ def _start(G0, b0, beta):
     return G, b
 
 
-@pytest.mark.parametrize("M", [1, 7, 63, 65, 129, 257])
-@pytest.mark.parametrize("n", [1, 31, 33, 300])
+# Workgroup x of knm_gram_kernel takes tile row bi = 8 (local / tiles_n) + xcd and tile column local % tiles_n (local = x >> 3,
+# xcd = x & 7; 128-row, 64-column tiles; grid 8 ceil(tiles_m / 8) tiles_n).  Up to M = 1024 the round local / tiles_n is 0.  The
+# smallest shapes at which the rest of that mapping runs:
+#   (1, 1025)   9 tile rows: bi = 8 is the first of round 1, on XCD 0, with one valid row (the half tile j0 = 1088 lies past M
+#               and returns); XCD slots 1 .. 7 of round 1 return; one k-tile of one row
+#   (33, 1025)  the same with two k-tiles, the second of one row
+#   (33, 1089)  M = 1024 + 65: bi = 8 has its diagonal tile and its half tile j0 = i0 + 64, the latter one column wide
+#   (40, 1153)  M = 9 x 128 + 1, 10 tile rows: round 1 on XCDs 0 and 1, bi = 8 full, bi = 9 one row
+#   (33, 2113)  M = 16 x 128 + 65, 17 tile rows: round 2 (bi = 16, XCD 0) with a one-column half tile; round 1 on all eight XCDs
+# A beta = 0 call starts from NaN everywhere, so a tile nobody visits fails isfinite and one stored elsewhere fails the bound.
+GRAM_SHAPES = [(n, M) for M in (1, 7, 63, 65, 129, 257) for n in (1, 31, 33, 300)]
+GRAM_SHAPES_PAST_ONE_ROUND = [(1, 1025), (33, 1025), (33, 1089), (40, 1153), (33, 2113)]
+
+
+@pytest.mark.parametrize("n,M", GRAM_SHAPES + GRAM_SHAPES_PAST_ONE_ROUND)
 def test_gram_kernel(be, n, M):
     """G and b against a longdouble evaluation under 2 (n + 4) u (|beta G0| + sum_r |w K K|) per entry (the gamma bound of an
     (n + 1)-term sum with one pre-rounded factor), for beta in {0, 1, 0.5}; G == G' bit for bit; nothing written outside
@@ -161,25 +174,32 @@ def test_gram_contract(be):
 
 
 def test_gram_over_row_halves_agrees_to_rounding(be):
-    """Two calls over row halves (the second accumulating) against one call: equal to the bound of the sums, not bit for bit."""
-    n, M = 300, 129
-    K, w, y, G0, b0 = _gram_inputs(n, M)
-    ldk, ldg = K.shape[1], G0.shape[1]
-    dK, dw, dy = torch.from_numpy(K).cuda(), torch.from_numpy(w).cuda(), torch.from_numpy(y).cuda()
-    G1, b1 = _start(G0, b0, 0.0)
-    _gram_call(be, dK, ldk, n, M, dw, dy, 0.0, G1, ldg, b1)
-    G2, b2 = _start(G0, b0, 0.0)
-    h = 157
-    _gram_call(be, dK, ldk, h, M, dw, dy, 0.0, G2, ldg, b2)
-    _gram_call(be, dK[h:], ldk, n - h, M, dw[h:], dy[h:], 1.0, G2, ldg, b2)
-    Sabs = (np.abs(w[:n])[:, None] * np.abs(K[:, :M]).astype(np.float64)).T @ np.abs(K[:, :M]).astype(np.float64)
-    assert (np.abs(G1.cpu().numpy()[:M, :M] - G2.cpu().numpy()[:M, :M]) <= 4.0 * (n + 4) * U * Sabs).all()
-    assert torch.equal(G2[:M, :M], G2[:M, :M].t())
+    """Two calls over row halves (the second accumulating) against one call: equal to the bound of the sums, not bit for bit.
+    At M = 1089 the second call reads and adds to the tiles of the second round of tile rows (bi = 8, its half tile included)."""
+    for n, M, h in ((300, 129, 157), (65, 1089, 33)):
+        K, w, y, G0, b0 = _gram_inputs(n, M)
+        ldk, ldg = K.shape[1], G0.shape[1]
+        dK, dw, dy = torch.from_numpy(K).cuda(), torch.from_numpy(w).cuda(), torch.from_numpy(y).cuda()
+        G1, b1 = _start(G0, b0, 0.0)
+        _gram_call(be, dK, ldk, n, M, dw, dy, 0.0, G1, ldg, b1)
+        G2, b2 = _start(G0, b0, 0.0)
+        _gram_call(be, dK, ldk, h, M, dw, dy, 0.0, G2, ldg, b2)
+        _gram_call(be, dK[h:], ldk, n - h, M, dw[h:], dy[h:], 1.0, G2, ldg, b2)
+        Sabs = (np.abs(w[:n])[:, None] * np.abs(K[:, :M]).astype(np.float64)).T @ np.abs(K[:, :M]).astype(np.float64)
+        err = np.abs(G1.cpu().numpy()[:M, :M] - G2.cpu().numpy()[:M, :M])
+        bar = 4.0 * (n + 4) * U * Sabs
+        print("n %d M %d halves at %d: max err / bar %.3f" % (n, M, h, float((err / bar).max())))
+        assert np.isfinite(G2.cpu().numpy()[:M, :M]).all() and (err <= bar).all(), (n, M)
+        assert torch.equal(G2[:M, :M], G2[:M, :M].t())
 
 
 # ------------------------------------------------------------------ B. odx_symvn_f64
-@pytest.mark.parametrize("nv", [1, 2, 3, 8])
-@pytest.mark.parametrize("M", [1, 2, 63, 129, 1000])
+# (M, nv) past M = 1000: 1025 (257 row blocks of four rows, the last with one row; the odd last element) and 4099 (1025 row
+# blocks, 257 workgroups, 32 steps of the 16-byte loop and a ragged 33rd), for each of the three instantiations
+SYMVN_SHAPES = [(M, nv) for nv in (1, 2, 3, 8) for M in (1, 2, 63, 129, 1000)] + [(M, nv) for nv in (1, 3, 8) for M in (1025, 4099)]
+
+
+@pytest.mark.parametrize("M,nv", SYMVN_SHAPES)
 def test_symvn(be, M, nv):
     """Y against a longdouble evaluation under 2 (M + 2) u |alpha| (|G| |x|); NaN in the pad columns of G, X and Y (never read,
     never written); alpha applied once; the same bits twice; with two vectors, each column agrees with its own call."""
@@ -278,7 +298,11 @@ def test_backend_wrappers(be):
 
 
 # ------------------------------------------------------------------ C. odx.IncrementalFalkon end to end
-SHAPES = [(777, 129, 36, 5.0, 1e-3), (1500, 257, 70, 5.0, 1e-4), (3000, 300, 1024, 15.0, 1e-5)]
+# The last shape has 9 tile rows of 128 centres, a second round of odx_knm_gram_f64's tile rows.  It is benign enough for the
+# parity bars: oracle/falkon_ref alone, iterating on a K block evaluated in f32 (entries within 9.7e-6 of the f64 ones) instead of
+# the f64 block, gives alpha within 5.8e-7 relative and the scores within 3.9e-6 of the f64 fit, alpha within 3.9e-7 after the
+# removal (with the f64 entries rounded to f32: 5.3e-10, 1.8e-9, 7.1e-10) — more than an order of magnitude inside 1e-4.
+SHAPES = [(777, 129, 36, 5.0, 1e-3), (1500, 257, 70, 5.0, 1e-4), (3000, 300, 1024, 15.0, 1e-5), (2600, 1100, 36, 5.0, 1e-3)]
 _refs = {}
 
 

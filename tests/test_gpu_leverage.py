@@ -48,11 +48,19 @@ def _rowquad_inputs(n, M):
     return K, Li
 
 
-@pytest.mark.parametrize("M", [1, 7, 16, 17, 128, 129, 257])
-@pytest.mark.parametrize("n", [1, 127, 129, 300])
+# (n, M) past M = 257: 17 and 18 column tiles of 64, the last of one column (M = 1024 + 1 and 1024 + 65), the factor's clean
+# loader form kt + BK <= j0 over up to 64 and 68 k-tiles of 16 with a ragged k-tile of one column behind them, two row blocks
+# of K with 1 and 2 rows in the second
+ROWQUAD_SHAPES = [(n, M) for M in (1, 7, 16, 17, 128, 129, 257) for n in (1, 127, 129, 300)] + [(129, 1025), (130, 1089)]
+
+
+@pytest.mark.parametrize("n,M", ROWQUAD_SHAPES)
 def test_rowquad_kernel(be, n, M):
     """q against an extended-precision evaluation under 4 (M + 2) u sum_j (sum_c |K_rc| |Li_jc|)^2; NaN in every cell the
-    kernel must not use; nothing written past row n; the same bits twice and for a row sub-block."""
+    kernel must not use; nothing written past row n; the same bits twice and for a row sub-block.  (The bar holds no width:
+    (M + 2) u bounds the M-term sum T_rj within (M + 2) u S_rj, its square within twice that of S_rj^2, and the sum of the M
+    squares adds (M + 2) u of itself: 3 (M + 2) u to first order, 4 with the second-order terms while M u << 1.)  Past
+    M = 257 the factor at a leading dimension of the other parity (16-byte loads for 8-byte ones) gives the same bits as well."""
     K, Li = _rowquad_inputs(n, M)
     Lt = np.tril(np.nan_to_num(Li[:, :M])).astype(np.longdouble)
     Kx = K[:, :M].astype(np.longdouble)
@@ -62,9 +70,10 @@ def test_rowquad_kernel(be, n, M):
     bar = (4.0 * (M + 2) * U * (S * S).sum(1)).astype(np.float64)
     dK, dL = torch.from_numpy(K).cuda(), torch.from_numpy(Li).cuda()
 
-    def call(k, rows):
+    def call(k, rows, L=None):
+        L = dL if L is None else L
         q = torch.full((rows + 3,), -7.0, dtype=torch.float64, device="cuda")
-        rc = be.lib.odx_knm_rowquad_f64(_p(k), K.shape[1], rows, M, _p(dL), Li.shape[1], _p(q), be._stream())
+        rc = be.lib.odx_knm_rowquad_f64(_p(k), K.shape[1], rows, M, _p(L), L.shape[1], _p(q), be._stream())
         assert rc == 0, be.lib.odx_last_error_string()
         q = q.cpu().numpy()
         assert (q[rows:] == -7.0).all(), "written past row n"
@@ -77,6 +86,10 @@ def test_rowquad_kernel(be, n, M):
     assert np.array_equal(call(dK, n), q), "two calls differ"
     lo, hi = (37, 201) if n >= 201 else (min(37, n - 1), n)
     assert np.array_equal(call(dK[lo:], hi - lo), q[lo:hi]), "a row sub-block gives other bits"
+    if M > 257:
+        other = torch.full((M, Li.shape[1] + 1), float("nan"), dtype=torch.float64, device="cuda")
+        other[:, :M] = dL[:, :M]                                   # a leading dimension of the other parity: the other loads
+        assert np.array_equal(call(dK, n, other), q), "the factor at a leading dimension of the other parity gives other bits"
 
 
 def test_rowquad_contract(be):
@@ -117,9 +130,12 @@ def _direct(Z, sigma, kind):
     return ((1 + u) if kind == 1 else (1 + u + u * u / 3.0)) * np.exp(-u)
 
 
-@pytest.mark.parametrize("D", [36, 1024])
-@pytest.mark.parametrize("M", [7, 130, 257])
-@pytest.mark.parametrize("kind", [0, 1, 2])
+# (kind, M, D); M = 1025: five column blocks of 256 in kmm_epilogue_kernel (the last of one column), 9 row blocks of 128 in the
+# Gram GEMM's lower tiles
+KMM_SHAPES = [(kind, M, D) for D in (36, 1024) for M in (7, 130, 257) for kind in (0, 1, 2)] + [(kind, 1025, 36) for kind in (0, 1, 2)]
+
+
+@pytest.mark.parametrize("kind,M,D", KMM_SHAPES)
 def test_radial_kmm(be, kind, M, D):
     """Per entry 8 D u (|z_i|^2 + |z_j|^2) s, s the kernel's largest slope in d^2 (1 / (2 sigma^2), x 3 and x 5/3 for the Matern
     kinds); the diagonal addition is one rounding."""
@@ -163,7 +179,7 @@ def test_radial_kmm(be, kind, M, D):
 
 
 # ------------------------------------------------------------------ C. chol_inverse
-@pytest.mark.parametrize("M", [7, 130, 257])
+@pytest.mark.parametrize("M", [7, 130, 257, 1025])
 def test_chol_inverse(be, M):
     """Li against numpy's inverse of the f64 Cholesky factor of the same matrix, to 1e-7 max(1, |Li|_max) (the bar
     test_gpu_matern.py::test_preconditioner holds the same chain to); A itself is left alone; a negative pivot raises."""
@@ -199,7 +215,10 @@ def test_row_quad_refuses_other_formats(be):
 
 
 # ------------------------------------------------------------------ D. leverage_scores
-CASES = {"a": (300, 130, 70, 10.0, 1e-3), "b": (513, 257, 70, 5.0, 1e-3), "c": (333, 130, 1024, 15.0, 1e-4)}
+# "d": one dictionary of 1100 centres (18 column tiles in the row quadratic form, 9 blocks of 128 in the dictionary's matrix and
+# its inverse factor) against 1300 rows, 11 row blocks of K
+CASES = {"a": (300, 130, 70, 10.0, 1e-3), "b": (513, 257, 70, 5.0, 1e-3), "c": (333, 130, 1024, 15.0, 1e-4),
+         "d": (1300, 1100, 36, 5.0, 1e-3)}
 _cases = {}
 
 
