@@ -741,6 +741,30 @@ int odx_knm_fwd_bwd_rw(const float* K, int64_t ldk, int64_t n, int64_t M, const 
 int odx_logistic_rows_f64(const double* t, const double* y, int64_t n, double neg_weight, double* g, double* w, double* l,
                           odx_stream_t stream);
 
+/* ---------------------------------------------------------------- sample-weighted FALKON (odx/weighted.py)
+ * The squared loss with a weight per row, (1 / n) sum_i w_i (f_i - y_i)^2: the CG's product is K' (w o (K v)).
+ *
+ * odx_knm_fwd_bwd_q_rw:  out[j] = sum_{r < n} K[r, j] d[r] t[r],  t[r] = sum_j K[r, j] v[j],  from ONE read of a compact-format
+ * block (K, Klo, fmt as odx_knm_fwd_bwd_q takes them: ODX_KNM_U24 or ODX_KNM_BF16, K 8-byte aligned, ldk % 8 == 0,
+ * ldk >= roundup(M, 8), the low-byte plane 4-byte aligned with the same rule for ldlo), every M from 1 to 20440 — the widths
+ * above 5084 are the ones odx_knm_fwd_bwdn_q_rw does not reach.  v: M doubles.  d: n doubles or NULL — NULL means ones, and
+ * gives the same bits as a vector of ones; a weight of exactly 0 removes its row; negative weights are legal.  t_out (n doubles
+ * or NULL) receives t as reduced, BEFORE the weight; `out` is the same bits with or without it.  Rows past n and columns past M
+ * contribute nothing, whatever the pad holds (nothing is read past row n - 1; a pad column meets a zero, and the bf16 form
+ * clears its bit pattern first).  There is no column map.  Workspace: odx_knm_fwd_bwd_q_workspace_bytes(n, M, fmt), that
+ * entry's slabs, as odx_knm_fwd_bwd_rw takes its f32 twin's: this entry has a configuration table of its own, whose workgroups
+ * per compute unit are at every width at most the slabs per compute unit of that entry, and it needs
+ * min(CUs x workgroups per CU, row blocks) x roundup(M, 4) doubles of it (less is ODX_ERR_WORKSPACE).  The grid covers the
+ * whole device: odx_set_pass_cus and odx_set_pass_reserved_cus are not honoured.  The persistent row blocks of
+ * odx_knm_fwd_bwd_q's barrier form at every width (no free-running halves); a block's weights are loaded ahead of its row dots
+ * and multiplied once into the reduced dots.  f64 sums in a fixed order, no atomics: the same call twice gives the same bits.
+ * n <= 0: out = 0.
+ * ODX_ERR_UNSUPPORTED above M = 20440, ODX_ERR_WORKSPACE, ODX_ERR_INVALID for a null K, v or out, another format, a missing
+ * low-byte plane and a misaligned K. */
+int odx_knm_fwd_bwd_q_rw(const void* K, int64_t ldk, const void* Klo, int64_t ldlo, int fmt, int64_t n, int64_t M,
+                         const double* v, const double* d, double* out, double* t_out, void* workspace, int64_t workspace_bytes,
+                         odx_stream_t stream);
+
 /* ---------------------------------------------------------------- A7: RLS box regressors
  * RegionRefinerTrainer.train / solve
  * (src/modules/region-refiner/region_refiner_trainer/train_region_refiner.py:25-119):

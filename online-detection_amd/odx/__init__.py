@@ -8,7 +8,8 @@ from .falkon import Falkon, FalkonOptions, GaussianKernel, InCoreFalkon, MaternK
 from .leverage import LeverageSelector, leverage_scores  # noqa: F401
 from .incremental import IncrementalFalkon  # noqa: F401
 from .logistic import LogisticFalkon, LogisticLoss, falkon_fit_logistic  # noqa: F401
+from .weighted import falkon_fit_weighted  # noqa: F401
 
 __all__ = ["hip", "options", "get_backend", "set_backend", "SolverOptions", "falkon_fit", "falkon_fit_lockstep", "falkon_fit_path", "falkon_fit_multi", "falkon_fit_grid", "falkon_fit_cv", "falkon_fit_stats", "cv_folds", "Falkon", "InCoreFalkon",
            "GaussianKernel", "MaternKernel", "FalkonOptions", "predict_path", "predict_grid", "leverage_scores", "LeverageSelector", "IncrementalFalkon", "LogisticFalkon", "LogisticLoss",
-           "falkon_fit_logistic"]
+           "falkon_fit_logistic", "falkon_fit_weighted"]

@@ -24,6 +24,7 @@ from .knm_path import PathOps, _p
 from .incremental_ops import IncrementalOps
 from .leverage_ops import LeverageOps
 from .logistic_ops import LogisticOps
+from .weighted_ops import WeightedOps
 
 
 B16_DTYPES = (torch.bfloat16, torch.float16)
@@ -153,7 +154,7 @@ class KnmStream:
         self.K, self.fmt, self.lo = F.P, "stream", None
 
 
-class HipBackend(PathOps, LeverageOps, IncrementalOps, LogisticOps):
+class HipBackend(PathOps, LeverageOps, IncrementalOps, LogisticOps, WeightedOps):
     name = "hip-gfx950"
     # The smallest number of columns for which a dense mmv (ranges None, gauss "h2") goes through odx_gauss_mmvn_h2: K(X, Z)
     # evaluated once per group of up to 8 columns instead of once per column, the same bits.  An attribute like

@@ -149,8 +149,11 @@ class _FalkonBase:
     _cpu_model = False
 
     def __init__(self, kernel, penalty, M, center_selection="uniform", maxiter=20, seed=None,
-                 error_fn=None, error_every=1, options=None, **_ignored):
+                 error_fn=None, error_every=1, options=None, weight_fn=None, **_ignored):
         self.kernel = kernel
+        # falkon's weight_fn(Y, X, indices) -> one weight per row (None: the unweighted fit, as ever).  With it, fit() is the
+        # sample-weighted squared-loss fit (odx/weighted.py) and every other fit method refuses.
+        self.weight_fn = weight_fn
         self.penalty = penalty
         self.M = M
         self.maxiter = maxiter
@@ -161,13 +164,77 @@ class _FalkonBase:
         self.ny_points_ = None
 
     def fit(self, X, Y, Xts=None, Yts=None):
+        if self.__dict__.get("weight_fn") is not None:
+            return self._fit_weighted(X, Y)
         return self._fit(X, Y, multi=False)
+
+    def _no_weights(self, what):
+        """The fit methods that know no row weights refuse an estimator with a weight_fn instead of fitting unweighted."""
+        if self.__dict__.get("weight_fn") is not None:
+            raise NotImplementedError("%s: sample weights (weight_fn) are offered by fit(X, Y) only; %s would fit unweighted"
+                                      % (type(self).__name__, what))
+
+    def _fit_weighted(self, X, Y):
+        """fit(X, Y) with a weight_fn: the centres WITH their labels and indices, the weights of the rows
+        (weight_fn(Y, X, None)) and of the centres (weight_fn(Y_Z, Z, idx)), then weighted.falkon_fit_weighted.  Uniform
+        selection has the indices; a ``center_selection`` object is called as ``select(X, Y)`` and must return ``(Z, Y_Z)``
+        or ``(Z, Y_Z, idx)`` (LogisticFalkon's rule; idx is None for the first form)."""
+        from .weighted import falkon_fit_weighted
+        name = type(self).__name__
+        be = _backend.get_backend()
+        F = be.features(X)
+        y = torch.as_tensor(Y).reshape(F.n, -1)
+        if y.shape[1] != 1:
+            raise ValueError("odx FALKON fits one right-hand side per model (the reference trains one "
+                             "binary classifier per fit); got Y with %d columns" % y.shape[1])
+        y = y.to(F.X.device)
+        if isinstance(self.center_selection, str):
+            gen = None
+            if self.seed is not None:
+                gen = torch.Generator()
+                gen.manual_seed(int(self.seed))
+            idx = torch.randperm(F.n, generator=gen)[: self.M]
+            Zf = be.rows(F, idx)
+            yz = y[idx.to(y.device)]
+        else:
+            sel = self.center_selection.select(F.X, y)
+            if not isinstance(sel, tuple) or len(sel) not in (2, 3) or sel[1] is None:
+                raise ValueError("%s: with a weight_fn, center_selection.select(X, Y) must return (Z, Y_Z) or (Z, Y_Z, idx): "
+                                 "the centres with their labels" % name)
+            Zf = be.features(sel[0])
+            yz = torch.as_tensor(sel[1]).reshape(-1, 1).to(F.X.device)
+            idx = sel[2] if len(sel) == 3 else None
+            if yz.shape[0] != Zf.n:
+                raise ValueError("%s: the selector returned %d centres and %d labels" % (name, Zf.n, yz.shape[0]))
+        self.M = Zf.n
+
+        def weights(lab, rows, ind, count, what, total):
+            wv = torch.as_tensor(self.weight_fn(lab, rows, ind)).reshape(-1).to(torch.float64)
+            if wv.numel() != count:
+                raise ValueError("%s: weight_fn returned %d weights for %s, expected %d" % (name, wv.numel(), what, count))
+            if not bool(torch.isfinite(wv).all()) or bool((wv < 0).any()) or (total and not float(wv.sum()) > 0.0):
+                raise ValueError("%s: the weights of %s must be finite and >= 0%s" % (name, what, " with a positive sum" if total else ""))
+            return be.vec(wv)
+        w = weights(y, F.X, None, F.n, "the rows", True)
+        wz = weights(yz, Zf.X, idx, Zf.n, "the centres", False)
+        alpha = falkon_fit_weighted(be, F, be.vec(y[:, 0]), w, Zf, wz, _kernel_arg(self.kernel), float(self.penalty),
+                                    int(self.maxiter), self.options.solver_options()).reshape(-1, 1)
+        if hasattr(be, "release_helper_streams"):
+            be.release_helper_streams()
+        self.alpha_ = alpha
+        self.ny_points_ = Zf.X.contiguous() if Zf.X.stride(0) != Zf.D else Zf.X
+        if self._cpu_model:
+            self.alpha_, self.ny_points_ = self.alpha_.cpu(), self.ny_points_.cpu()
+        else:
+            self._centres(Zf)
+        return self
 
     def fit_multi(self, X, Y):
         """Fit the T >= 1 columns of Y (n, T) as T outputs of ONE model over the same rows and centres, from one K_nM block
         and one preconditioner (solver.falkon_fit_multi): `alpha_` becomes (M, T) and `predict` returns (n, T), as the upstream
         estimator's fit does for a label matrix.  Centres, `ny_points_` and the centre cache are handled as by `fit`; one column
         takes `fit`'s code path, bit for bit.  (`fit` itself keeps refusing more than one column.)"""
+        self._no_weights("fit_multi")
         return self._fit(X, Y, multi=True)
 
     def _fit(self, X, Y, multi):
@@ -211,6 +278,7 @@ class _FalkonBase:
         template and stays as it is.  Under knm_storage "stream" (no block: K is recomputed by the passes) up to 8 penalties
         cost one recompute of K per CG iteration, 9 .. 16 one per iteration plus one per full residual."""
         import copy
+        self._no_weights("fit_path")
         be = _backend.get_backend()
         F = be.features(X)
         if isinstance(self.center_selection, str):
@@ -248,6 +316,7 @@ class _FalkonBase:
         assignment with values in [0, folds); None: cv_folds(n, folds, seed), which leaves the global RNG alone.  This
         estimator is the template and stays as it is."""
         import copy
+        self._no_weights("fit_cv")
         be = _backend.get_backend()
         F = be.features(X)
         if isinstance(self.center_selection, str):
@@ -295,6 +364,7 @@ class _FalkonBase:
         and shared by all members (`ny_points_`); each member has its own GaussianKernel(sigma), `penalty` and `alpha_`.
         This estimator is the template and stays as it is."""
         import copy
+        self._no_weights("fit_grid")
         _grid_refuse(self.kernel, "fit_grid")
         be = _backend.get_backend()
         F = be.features(X)
@@ -440,6 +510,14 @@ def predict_grid(estimators, X):
     return res
 
 
+def _refuse_weighted(estimators, what):
+    """The batched fits know no row weights: an estimator with a weight_fn is refused instead of fitted unweighted."""
+    for est in estimators:
+        if getattr(est, "weight_fn", None) is not None:
+            raise NotImplementedError("%s: sample weights (weight_fn) are offered by fit(X, Y) only; the batched fit would "
+                                      "fit %s unweighted" % (what, type(est).__name__))
+
+
 def fit_batch(estimators, Xs, Ys, streams=None):
     """Fit several independent estimators (the classes of one Minibootstrap round) with ONE batched preconditioner
     launch chain (backend.precond_batched) instead of one ~400-launch chain each; the K_nM build and the CG of every
@@ -447,6 +525,7 @@ def fit_batch(estimators, Xs, Ys, streams=None):
     slice of the batched factors.  Every estimator ends up exactly as its own ``fit(X, Y)`` would leave it (same bits:
     the batched factors equal the single-class ones).  The reference has no counterpart: it trains the classes one
     after the other (OnlineRegionClassifier_incore.py:96-155)."""
+    _refuse_weighted(estimators, "fit_batch")
     be = _backend.get_backend()
     if not hasattr(be, "precond_batched"):
         for est, X, Y in zip(estimators, Xs, Ys):
@@ -618,6 +697,8 @@ class BatchFit:
         the most centres any class can have (the block's slot size: a later group with more centres than the first group's
         largest class would otherwise force everything through the general path)."""
         be = self.be
+        estimators = list(estimators)
+        _refuse_weighted(estimators, "BatchFit")
         first = len(self.est)
         self.est += list(estimators)
         self.Xs += list(Xs)

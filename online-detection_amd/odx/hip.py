@@ -181,6 +181,7 @@ SIGNATURES = {
     "odx_symvn_f64": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _f64, _vp, _i64, _vp]),
     "odx_knm_fwd_bwd_rw": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_logistic_rows_f64": (_i32, [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
+    "odx_knm_fwd_bwd_q_rw": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_rls_gram_workspace_bytes": (_i64, [_i64, _i32]),
     "odx_rls_gram_f64": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "odx_rls_solve_workspace_bytes": (_i64, [_i32]),
