@@ -707,12 +707,25 @@ int odx_radial_kmm_f64(const double* Zd, int64_t ldz, int64_t M, int D, double s
  * is w y); one workgroup owns a 128 x 64 output tile and walks the rows in ascending k-tiles of 32: no atomics, no workspace,
  * the same call twice gives the same bits.  Two calls over row halves equal one call to rounding only.
  *
+ * odx_knm_gram_rhsn_f64:  odx_knm_gram_f64's G from the same arguments, bit for bit, and nt right-hand sides from the same read,
+ *                    B[t * ldb + j] = beta B[t * ldb + j] + sum_{r < n} (w[r] Y[r * ldy + t]) K[r, j]   (t < nt, j < M).
+ * Y: the (n, nt) f64 label matrix, row-major, 16-byte aligned, ldy >= nt, ldy even.  B: nt rows of M doubles, 8-byte aligned,
+ * ldb >= M, not overlapping G.  1 <= nt <= 1024.  Y[r][t >= nt], the rows past n and B[t][j >= M] are never read or written;
+ * with beta == 0 B and G are never read.  n <= 0: only the scale by beta; M <= 0: nothing.  ODX_ERR_INVALID for a null or
+ * misaligned Y or B, ldy < nt or odd, ldb < M, nt out of range, B overlapping G, and what odx_knm_gram_f64 refuses.  The
+ * right-hand sides are further 128 x 64 tiles of the launch (128 columns of K against 64 label columns, the B operand
+ * w o Y, rounded once), on the same matrix instruction, stored transposed: no atomics, no workspace, one order of additions.
+ * Row t of B does not depend, bit for bit, on nt or on the other columns of Y; at nt = 1 it equals odx_knm_gram_f64's b to
+ * rounding only (the order of the sum differs).
+ *
  * odx_symvn_f64:  Y[q] = alpha * G X[q] for q < nv, 1 <= nv <= 8, from ONE read of the full M x M f64 matrix G (16-byte
  * aligned, ldg even, ldg >= M; G[., c >= M] is never read).  X / Y: nv f64 rows, ldx / ldy doubles apart; X rows 16-byte
  * aligned, ldx even; the doubles Y spans must not overlap those X spans (ODX_ERR_INVALID).  Rows as dot products with odx_trmvn_f64's loads and reduction; sums in a fixed
  * order, no scratch. */
 int odx_knm_gram_f64(const float* K, int64_t ldk, int64_t n, int64_t M, const double* w, const double* y, double beta,
                      double* G, int64_t ldg, double* b, odx_stream_t stream);
+int odx_knm_gram_rhsn_f64(const float* K, int64_t ldk, int64_t n, int64_t M, const double* w, const double* Y, int64_t ldy, int nt,
+                          double beta, double* G, int64_t ldg, double* B, int64_t ldb, odx_stream_t stream);
 int odx_symvn_f64(const double* G, int64_t ldg, int64_t M, int nv, const double* X, int64_t ldx, double alpha, double* Y,
                   int64_t ldy, odx_stream_t stream);
 

@@ -4,6 +4,9 @@
 //                      ROWS staged as [k][column], 128 x 64 lower tiles, three workgroups per CU, the skinny products on the
 //                      vector ALU in the first tile column — with contiguous rows, the row weight folded into the B operand on
 //                      its way into LDS (which therefore holds doubles), a read-modify-write epilogue and a mirrored store.
+//   odx_knm_gram_rhsn_f64 : the same G, and B[t] = beta B[t] + K' (w o Y[:, t]) for nt label columns from the same read: the
+//                      right-hand sides are further tile columns of the launch, 64 label columns wide, whose B operand is
+//                      w o Y[k-tile, t0 : t0 + 64] (doubles already) and whose 128 x 64 accumulators are stored transposed.
 //   odx_symvn_f64    : Y[q] = alpha G X[q] for up to 8 vectors from one read of the full matrix (trmvn_f64_kernel's rows, loads
 //                      and reduction over the whole row).
 // Neither uses scratch or atomics: one workgroup (one wave) owns an output tile (a row block) and sums in one fixed order.
@@ -33,11 +36,17 @@ __device__ __forceinline__ f32x2g kg_load2(const float* __restrict__ x, int col,
 // lie strictly above the diagonal, so the four waves share the LOWER 64 x 64 block, 32 x 32 each, and issue half the matrix
 // instructions; every other tile's waves own 64 x 32 outputs each.  XTY: the tile also forms its 128 entries of b (the tiles of
 // the first tile column when y is given).  Both are template arguments so that the k loop holds no branch.
-template <bool HALF, bool XTY>
+// RHS (knm_gram_rhsn_kernel; neither HALF nor XTY): the tile is 128 columns of K against 64 label columns, j0 the first of them.
+// y is then the (n, nt) row-major label matrix, ldy doubles a row; the B operand is w o Y[k-tile, j0 : j0 + 64], zero past column
+// nt; the accumulators (K column i0 + i, label column j0 + t) go to bout[(j0 + t) * ldb + i0 + i], transposed through LDS as the
+// mirror store is, with beta applied from bout.  G is not touched.
+template <bool HALF, bool XTY, bool RHS = false>
 __device__ __forceinline__ void knm_gram_tile(const float* __restrict__ K, int64_t ldk, int64_t n, int M, const double* __restrict__ w,
                                               const double* __restrict__ y, double beta, double* G, int64_t ldg, double* bout, int i0,
-                                              int j0, float* lds_a, double* lds_b, double* lds_wy) {
-  constexpr bool half = HALF, xty = XTY;
+                                              int j0, float* lds_a, double* lds_b, double* lds_wy, int64_t ldy = 0, int nt = 0,
+                                              int64_t ldb = 0) {
+  constexpr bool half = HALF, xty = XTY, rhs = RHS;
+  static_assert(!(RHS && (HALF || XTY)), "a right-hand-side tile is a full tile without the skinny product");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int arow = half ? 64 + wr * 32 : wr * 64;
@@ -51,7 +60,18 @@ __device__ __forceinline__ void knm_gram_tile(const float* __restrict__ K, int64
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     cb[q] = j0 + q * 32 + seg * 2;
-    mb[q] = cb[q] + 1 < M ? 2 : (cb[q] < M ? 1 : 0);
+    const int nb = rhs ? nt : M;                              // (the B side's columns: label columns in a right-hand-side tile)
+    mb[q] = cb[q] + 1 < nb ? 2 : (cb[q] < nb ? 1 : 0);
+  }
+  // RHS: the label columns this thread loads, clamped to nt - 1, so that the k loop loads without a branch and never reads a
+  // column >= nt; what a clamped load brings is dropped on the way into LDS (mb)
+  int cy[2][2] = {{0, 0}, {0, 0}};
+  if constexpr (rhs) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      cy[q][0] = cb[q] < nt ? cb[q] : nt - 1;
+      cy[q][1] = cb[q] + 1 < nt ? cb[q] + 1 : nt - 1;
+    }
   }
   int aoff[4];                                                // (a half tile has two row blocks: it reads them twice, in bounds)
 #pragma unroll
@@ -63,6 +83,7 @@ __device__ __forceinline__ void knm_gram_tile(const float* __restrict__ K, int64
     for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = f64x4g{0.0, 0.0, 0.0, 0.0};
   const int64_t nk = n > 0 ? (n + KG_BK - 1) / KG_BK : 0;
   f32x2g ra[2][4], rb[2][2];
+  f64x2g rbd[2][2];                                           // (RHS: the B side's entries, doubles)
   double rw[2] = {1.0, 1.0}, ry[2] = {0.0, 0.0};
   bool valid[2] = {false, false};
   // the rows of k-tile kt this thread stages, into registers: a row past n is not read (its place takes row n - 1's values, which
@@ -75,7 +96,14 @@ __device__ __forceinline__ void knm_gram_tile(const float* __restrict__ K, int64
 #pragma unroll
     for (int q = 0; q < 4; ++q) ra[h][q] = kg_load2(x, ca[q], ma[q]);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) rb[h][q] = kg_load2(x, cb[q], mb[q]);
+    for (int q = 0; q < 2; ++q) {
+      if constexpr (rhs) {
+        const double* yr = y + r * ldy;
+        rbd[h][q] = f64x2g{yr[cy[q][0]], yr[cy[q][1]]};
+      } else {
+        rb[h][q] = kg_load2(x, cb[q], mb[q]);
+      }
+    }
     if (w != nullptr) rw[h] = w[r];
     if (xty) ry[h] = y[r];
   };
@@ -98,8 +126,13 @@ __device__ __forceinline__ void knm_gram_tile(const float* __restrict__ K, int64
         *reinterpret_cast<f32x2g*>(da + q * 32) = f32x2g{ok ? ra[h][q][0] : 0.f, ok ? ra[h][q][1] : 0.f};
       // the row weight, once per entry of the B operand: w K in f64 (one rounding; w = 1 changes no bit)
 #pragma unroll
-      for (int q = 0; q < 2; ++q)
-        *reinterpret_cast<f64x2g*>(db + q * 32) = f64x2g{ok ? rw[h] * (double)rb[h][q][0] : 0.0, ok ? rw[h] * (double)rb[h][q][1] : 0.0};
+      for (int q = 0; q < 2; ++q) {
+        if constexpr (rhs)                                     // w y, rounded once as an XTY tile rounds it
+          *reinterpret_cast<f64x2g*>(db + q * 32) =
+              f64x2g{ok && mb[q] >= 1 ? rw[h] * rbd[h][q][0] : 0.0, ok && mb[q] == 2 ? rw[h] * rbd[h][q][1] : 0.0};
+        else
+          *reinterpret_cast<f64x2g*>(db + q * 32) = f64x2g{ok ? rw[h] * (double)rb[h][q][0] : 0.0, ok ? rw[h] * (double)rb[h][q][1] : 0.0};
+      }
       if (xty && seg == 0) lds_wy[krow + 16 * h] = ok ? rw[h] * ry[h] : 0.0;
     }
     __syncthreads();
@@ -159,6 +192,30 @@ __device__ __forceinline__ void knm_gram_tile(const float* __restrict__ K, int64
   // through LDS, a 16 x 16 block per wave at a time, so that its stores run along G's rows as the lower ones do.
   __syncthreads();                                             // everyone is through with lds_b
   double* tr = lds_b + wave * (16 * 17);
+  if constexpr (rhs) {
+    // the 16 x 16 blocks as below, every entry stored at its transposed place only: 16 lanes run along a row of bout
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) {
+        const int r0 = i0 + arow + tm * 16, c0 = j0 + wc * 32 + tn * 16;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) tr[(kq + 4 * reg) * 17 + r16] = acc[tm][tn][reg];
+        __syncthreads();
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int row = r0 + r16, col = c0 + kq + 4 * reg;   // K column `row`, label column `col`
+          if (row < M && col < nt) {
+            double v = tr[r16 * 17 + kq + 4 * reg];
+            double* dst = bout + (int64_t)col * ldb + row;
+            if (beta != 0.0) v = fma(beta, *dst, v);
+            *dst = v;
+          }
+        }
+        __syncthreads();
+      }
+    return;
+  }
 #pragma unroll
   for (int tm = 0; tm < (half ? 2 : 4); ++tm)
 #pragma unroll
@@ -204,6 +261,36 @@ __global__ __launch_bounds__(256, 3) void knm_gram_kernel(const float* __restric
     knm_gram_tile<true, false>(K, ldk, n, M, w, y, beta, G, ldg, bout, i0, j0, lds_a, lds_b, lds_wy);
   else
     knm_gram_tile<false, false>(K, ldk, n, M, w, y, beta, G, ldg, bout, i0, j0, lds_a, lds_b, lds_wy);
+}
+
+// knm_gram_kernel's tiles with ceil(nt / 64) further tile columns behind the tiles_n of G: tile column tiles_n + c of tile row bi
+// holds B[64 c .. 64 c + 63][128 bi .. 128 bi + 127].  gridDim.x = 8 x ceil(tile rows / 8) x (tiles_n + ceil(nt / 64)).  The G tiles
+// keep knm_gram_kernel's map (XCD x walks the tile rows x, x + 8, ...); a tile row's lower tiles grow with its index, so XCD 7
+// carries the most of every round and XCD 0 the fewest, and the right-hand-side tiles go the other way round: those of tile row
+// 8 r + 7 - x run on XCD x.  The G tiles are knm_gram_tile<HALF, false>, so G has knm_gram_kernel's bits.
+__global__ __launch_bounds__(256, 3) void knm_gram_rhsn_kernel(const float* __restrict__ K, int64_t ldk, int64_t n, int M,
+                                                               const double* __restrict__ w, const double* __restrict__ Y,
+                                                               int64_t ldy, int nt, double beta, double* G, int64_t ldg, double* B,
+                                                               int64_t ldb) {
+  __shared__ __attribute__((aligned(16))) float lds_a[KG_BK * KG_LDA];
+  __shared__ __attribute__((aligned(16))) double lds_b[KG_BK * KG_LDB];
+  const int tiles_n = (M + KG_BN - 1) / KG_BN, tiles_all = tiles_n + (nt + KG_BN - 1) / KG_BN;
+  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
+  const int bj = local % tiles_all;
+  const int bi = 8 * (local / tiles_all) + (bj >= tiles_n ? 7 - xcd : xcd);
+  const int i0 = bi * KG_BM;
+  if (i0 >= M) return;
+  if (bj >= tiles_n) {
+    knm_gram_tile<false, false, true>(K, ldk, n, M, w, Y, beta, nullptr, 0, B, i0, (bj - tiles_n) * KG_BN, lds_a, lds_b, nullptr, ldy, nt,
+                                      ldb);
+    return;
+  }
+  const int j0 = bj * KG_BN;
+  if (j0 >= M || j0 > i0 + KG_BM - 1) return;                  // lower tiles only
+  if (j0 == i0 + 64)
+    knm_gram_tile<true, false>(K, ldk, n, M, w, nullptr, beta, G, ldg, nullptr, i0, j0, lds_a, lds_b, nullptr);
+  else
+    knm_gram_tile<false, false>(K, ldk, n, M, w, nullptr, beta, G, ldg, nullptr, i0, j0, lds_a, lds_b, nullptr);
 }
 
 // Y[q][i] = alpha * sum_{j < M} G[i][j] X[q][j] for q < nv <= NV vectors from ONE read of G: trmvn_f64_kernel (dense_f64.hip)
@@ -299,6 +386,36 @@ extern "C" int odx_knm_gram_f64(const float* K, int64_t ldk, int64_t n, int64_t 
   const int64_t nn = n > 0 ? n : 0;
   hipLaunchKernelGGL(knm_gram_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), K, ldk, nn, (int)M, w, y, beta, G, ldg, b);
   ODX_CHECK_LAUNCH("odx_knm_gram_f64");
+  return ODX_OK;
+}
+
+extern "C" int odx_knm_gram_rhsn_f64(const float* K, int64_t ldk, int64_t n, int64_t M, const double* w, const double* Y, int64_t ldy,
+                                     int nt, double beta, double* G, int64_t ldg, double* B, int64_t ldb, odx_stream_t stream) {
+  using namespace odx;
+  if (M <= 0) return ODX_OK;
+  ODX_REQUIRE(nt >= 1 && nt <= 1024, "odx_knm_gram_rhsn_f64: 1 .. 1024 label columns per call (got %d)", nt);
+  ODX_REQUIRE(G, "odx_knm_gram_rhsn_f64: null G");
+  ODX_REQUIRE(M < (1ll << 20), "odx_knm_gram_rhsn_f64: M must be below 2^20");
+  ODX_REQUIRE(ldg >= M && (reinterpret_cast<uintptr_t>(G) & 7u) == 0, "odx_knm_gram_rhsn_f64: G needs ldg >= M and 8-byte alignment");
+  ODX_REQUIRE(Y && aligned16(Y) && ldy >= nt && ldy % 2 == 0, "odx_knm_gram_rhsn_f64: Y must be 16-byte aligned with ldy even and ldy >= nt");
+  ODX_REQUIRE(B && (reinterpret_cast<uintptr_t>(B) & 7u) == 0 && ldb >= M, "odx_knm_gram_rhsn_f64: B needs ldb >= M and 8-byte alignment");
+  {  // the doubles G and B span must not share one (a tile of B is stored while other workgroups read and store G)
+    const double* ge = G + (M - 1) * ldg + M;
+    const double* be = B + (int64_t)(nt - 1) * ldb + M;
+    ODX_REQUIRE(ge <= B || be <= G, "odx_knm_gram_rhsn_f64: B must not overlap G");
+  }
+  if (n > 0) {
+    ODX_REQUIRE(K, "odx_knm_gram_rhsn_f64: null K");
+    ODX_REQUIRE(aligned16(K) && ldk % 4 == 0 && ldk >= M, "odx_knm_gram_rhsn_f64: K must be 16-byte aligned with ldk %% 4 == 0 and ldk >= M");
+  }
+  if (n <= 0 && beta == 1.0) return ODX_OK;
+  const int64_t tiles_m = ceil_div(M, KG_BM), tiles_all = ceil_div(M, (int64_t)KG_BN) + ceil_div((int64_t)nt, (int64_t)KG_BN);
+  const int64_t grid = 8 * ceil_div(tiles_m, 8) * tiles_all;
+  ODX_REQUIRE(grid < (1ll << 31), "odx_knm_gram_rhsn_f64: too many tiles");
+  const int64_t nn = n > 0 ? n : 0;
+  hipLaunchKernelGGL(knm_gram_rhsn_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), K, ldk, nn, (int)M, w, Y, ldy, nt, beta, G,
+                     ldg, B, ldb);
+  ODX_CHECK_LAUNCH("odx_knm_gram_rhsn_f64");
   return ODX_OK;
 }
 

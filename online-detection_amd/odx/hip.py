@@ -178,6 +178,7 @@ SIGNATURES = {
     "odx_knm_rowquad_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "odx_radial_kmm_f64": (_i32, [_vp, _i64, _i64, _i32, _f64, _i32, _vp, _f64, _vp, _i64, _vp, _vp]),
     "odx_knm_gram_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _i64, _vp, _vp]),
+    "odx_knm_gram_rhsn_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _f64, _vp, _i64, _vp, _i64, _vp]),
     "odx_symvn_f64": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _f64, _vp, _i64, _vp]),
     "odx_knm_fwd_bwd_rw": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "odx_logistic_rows_f64": (_i32, [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),

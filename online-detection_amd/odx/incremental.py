@@ -9,13 +9,19 @@ call with negated weights (``remove``), forgotten by a scale of all three (``dec
 with one read of G per iteration (``solver.falkon_fit_stats``) behind the preconditioner of the centres, which no row changes.
 The result is the FALKON iterate of a fit on all rows the statistics hold, up to f64 rounding (the K entries are the f32 ones of
 the stored-block fits; their products and sums are f64: odx_knm_gram_f64).
+
+Nothing in G depends on the labels: a model of T outputs (``outputs=T``) keeps ONE G and T right-hand sides, summed from the same
+read of each chunk (odx_knm_gram_rhsn_f64) and solved in lock step (``solver.falkon_fit_stats_multi``); and nothing in G, b or T's
+factors depends on the penalty: ``solve_path`` fits a lambda path from the same statistics (``solver.falkon_fit_stats_path``).
 """
+import math
+
 import torch
 
 from . import backend as _backend
 from .falkon import Falkon, GaussianKernel, MaternKernel, _FalkonBase, _kernel_arg
 from .leverage import BLOCK_BYTES, _block, _f32_rows
-from .solver import falkon_fit_stats
+from .solver import falkon_fit_stats, falkon_fit_stats_multi, falkon_fit_stats_path
 
 _DERIVED = ("_zf", "_P")          # rebuilt from ny_points_ / penalty on the next use: not copied, not pickled
 
@@ -26,17 +32,25 @@ class IncrementalFalkon(_FalkonBase):
     kernel: a GaussianKernel or a MaternKernel.  centres: the (M, D) Nystroem centres; None: they are selected from the rows of
     the FIRST ``partial_fit`` exactly as ``InCoreFalkon.fit`` selects them (``center_selection``, ``M``), and stay.  chunk_rows:
     rows per K block (default: as many as a 1 GiB f32 block holds); the block buffer is reused from chunk to chunk and dropped
-    when the call returns.  One label column per model.
+    when the call returns.  outputs: the number T of label columns (default: one label column per model).  With T > 1 the rows
+    carry a label matrix (n, T) — one-vs-rest heads over the same stream of rows and the same centres — and the model keeps one
+    G and T right-hand sides.  There is ONE weight per row, shared by the outputs (``sample_weight``, negated weights and
+    ``decay`` act on all of them): that sharing is what makes G shareable, and a weight per output would need T matrices G.
 
-    After a solve: ``alpha_`` (M, 1), ``ny_points_``, ``n_seen_`` (the total weight held), ``gram_`` (M, ld) and ``rhs_`` (M,).
+    After a solve: ``alpha_`` (M, 1), ``ny_points_``, ``n_seen_`` (the total weight held), ``gram_`` (M, ld) and ``rhs_`` (M,);
+    with outputs = T > 1 ``alpha_`` is (M, T), ``rhs_`` (T, Mp) with Mp = M rounded up to even, and ``predict`` returns (n, T).
     ``predict`` is the other estimators'; ``as_falkon()`` hands the fitted model out as a plain ``Falkon``."""
 
-    def __init__(self, kernel, penalty, M=None, centres=None, center_selection="uniform", maxiter=20, options=None, chunk_rows=None):
+    def __init__(self, kernel, penalty, M=None, centres=None, center_selection="uniform", maxiter=20, options=None, chunk_rows=None,
+                 outputs=1):
         if not isinstance(kernel, (GaussianKernel, MaternKernel)):
             raise ValueError("IncrementalFalkon: kernel must be a GaussianKernel or a MaternKernel, got %r" % (kernel,))
         if centres is None and isinstance(center_selection, str) and M is None:
             raise ValueError("IncrementalFalkon: needs centres, or M for the uniform selection from the first rows")
+        if isinstance(outputs, bool) or int(outputs) != outputs or not 1 <= int(outputs) <= 1024:
+            raise ValueError("IncrementalFalkon: outputs must be an integer in 1 .. 1024, got %r" % (outputs,))
         super().__init__(kernel, penalty, M, center_selection=center_selection, maxiter=maxiter, options=options)
+        self.outputs = int(outputs)
         self.centres = centres
         self.chunk_rows = chunk_rows
         self.n_seen_ = 0.0
@@ -86,7 +100,8 @@ class IncrementalFalkon(_FalkonBase):
         self.ny_points_ = Zf.X.contiguous() if Zf.X.stride(0) != Zf.D else Zf.X
         self._centres(Zf)
         self.gram_ = be.zeros(M * ((M + 1) // 2 * 2)).view(M, (M + 1) // 2 * 2)
-        self.rhs_ = be.zeros(M)
+        T = self.outputs
+        self.rhs_ = be.zeros(M) if T == 1 else be.zeros(T * ((M + 1) // 2 * 2)).view(T, (M + 1) // 2 * 2)
         self.n_seen_ = 0.0
         self.alpha_ = None
 
@@ -101,13 +116,20 @@ class IncrementalFalkon(_FalkonBase):
         if n < 1:
             raise ValueError("IncrementalFalkon: no rows")
         y = torch.as_tensor(Y).reshape(n, -1)
-        if y.shape[1] != 1:
+        T = self.outputs
+        if T == 1 and y.shape[1] != 1:
             raise ValueError("IncrementalFalkon fits one label column per model; got Y with %d columns" % y.shape[1])
+        if y.shape[1] != T:
+            raise ValueError("IncrementalFalkon(outputs=%d) takes Y with %d label columns; got %d" % (T, T, y.shape[1]))
         if self.ny_points_ is not None and F.D != self.ny_points_.shape[1]:
             raise ValueError("IncrementalFalkon: the rows have %d features, the centres %d" % (F.D, self.ny_points_.shape[1]))
         w = None
         if sample_weight is not None:
-            w = be.vec(torch.as_tensor(sample_weight).reshape(-1))
+            sw = torch.as_tensor(sample_weight)
+            if sw.dim() > 1 and sw.shape[-1] != 1 and sw.numel() != n:
+                raise ValueError("IncrementalFalkon: sample_weight must hold ONE weight per row, shared by the outputs; got %r "
+                                 "(a weight per output would need a G per output)" % (tuple(sw.shape),))
+            w = be.vec(sw.reshape(-1))
             if w.numel() != n:
                 raise ValueError("IncrementalFalkon: sample_weight must hold one weight per row (%d), got %d" % (n, w.numel()))
             total = float(w.sum())
@@ -126,7 +148,12 @@ class IncrementalFalkon(_FalkonBase):
         if self.ny_points_ is None:
             self._first(be, F)
         Zf, karg, M = self._centre_features(be), _kernel_arg(self.kernel), self.M
-        yv = be.vec(y[:, 0])
+        if T == 1:
+            yv = be.vec(y[:, 0])
+        else:
+            # the (n, T) label matrix with rows 16-byte aligned (T odd: one pad column, never read)
+            Yd = be.zeros(n * ((T + 1) // 2 * 2)).view(n, (T + 1) // 2 * 2)
+            Yd[:, :T] = be.vec(y)
         ldk = (M + 3) // 4 * 4
         chunk = self.chunk_rows
         if chunk is None:
@@ -140,7 +167,11 @@ class IncrementalFalkon(_FalkonBase):
             hi = min(n, lo + chunk)
             Fc = F if chunk >= n else be.rows(F, torch.arange(lo, hi))
             K = be.knm_f32(Fc, Zf, karg, n, out=buf) if buf is not None else _block(be, Fc, Zf, karg, n)
-            be.knm_gram(K, w=None if w is None else w[lo:hi], y=yv[lo:hi], beta=decay if lo == 0 else 1.0, G=self.gram_, b=self.rhs_)
+            wc, beta = None if w is None else w[lo:hi], decay if lo == 0 else 1.0
+            if T == 1:
+                be.knm_gram(K, w=wc, y=yv[lo:hi], beta=beta, G=self.gram_, b=self.rhs_)
+            else:
+                be.knm_gram_multi(K, w=wc, Y=Yd[lo:hi, :T], beta=beta, G=self.gram_, B=self.rhs_)
             del K
         self.n_seen_ = seen
         if solve:
@@ -173,8 +204,9 @@ class IncrementalFalkon(_FalkonBase):
         return self.partial_fit(X, Y)
 
     def _not_offered(self, *a, **k):
-        raise NotImplementedError("IncrementalFalkon: lambda paths, grids, cross-validation and several outputs from one G are "
-                                  "not offered; solve(penalty) refits one penalty from the same statistics")
+        raise NotImplementedError("IncrementalFalkon: fit_path, fit_multi, fit_grid and fit_cv are not offered: several outputs "
+                                  "from one G are the constructor's outputs=, a lambda path from the same statistics is "
+                                  "solve_path(penalties); grids and cross-validation are not offered")
 
     fit_multi = fit_path = fit_cv = fit_grid = _not_offered
 
@@ -186,12 +218,43 @@ class IncrementalFalkon(_FalkonBase):
         if penalty is not None:
             self.penalty = float(penalty)
         be = _backend.get_backend()
-        alpha = falkon_fit_stats(be, self.gram_, self.rhs_, self.n_seen_, self._precond(be), float(self.penalty), int(self.maxiter),
-                                 self.options.solver_options())
+        if self.outputs == 1:
+            alpha = falkon_fit_stats(be, self.gram_, self.rhs_, self.n_seen_, self._precond(be), float(self.penalty), int(self.maxiter),
+                                     self.options.solver_options()).reshape(-1, 1)
+        else:
+            alpha = falkon_fit_stats_multi(be, self.gram_, self.rhs_, self.n_seen_, self._precond(be), float(self.penalty),
+                                           int(self.maxiter), self.options.solver_options()).t().contiguous()      # (M, T)
         if hasattr(be, "release_helper_streams"):
             be.release_helper_streams()
-        self.alpha_ = alpha.reshape(-1, 1)
+        self.alpha_ = alpha
         return self
+
+    def solve_path(self, penalties):
+        """The models of a lambda path from G, b and n alone: one fitted ``Falkon`` per penalty, in the order given, from ONE
+        be.precond_path (the members share T's factors) and ONE lock-step run over all penalties and outputs
+        (solver.falkon_fit_stats_path): no K is built and no row is touched.  The members share one ``ny_points_`` tensor, so
+        ``odx.predict_path`` scores a path of one-output members from one kernel evaluation; a member of a model with T outputs
+        has ``alpha_`` (M, T).  This model's own ``penalty`` and ``alpha_`` stay as they are."""
+        if self.gram_ is None or not self.n_seen_ > 0.0:
+            raise RuntimeError("IncrementalFalkon.solve_path called before any rows were added")
+        lams = [float(x) for x in penalties]
+        if not lams or any(not (math.isfinite(x) and x > 0.0) for x in lams):
+            raise ValueError("IncrementalFalkon.solve_path: penalties must be a non-empty sequence of finite positive values, "
+                             "got %r" % (lams,))
+        be = _backend.get_backend()
+        opt = self.options.solver_options()
+        Ps = be.precond_path(self._centre_features(be), _kernel_arg(self.kernel), lams, opt.pc_epsilon)
+        B = self.rhs_ if self.outputs > 1 else self.rhs_.view(1, -1)
+        alphas = falkon_fit_stats_path(be, self.gram_, B, self.n_seen_, Ps, lams, int(self.maxiter), opt)
+        if hasattr(be, "release_helper_streams"):
+            be.release_helper_streams()
+        ny = self.ny_points_.clone().cpu()
+        members = []
+        for l, lam in enumerate(lams):
+            est = Falkon(self.kernel, lam, self.M, maxiter=self.maxiter, options=self.options)
+            est.alpha_, est.ny_points_ = alphas[l].t().contiguous().cpu(), ny
+            members.append(est)
+        return members
 
     def as_falkon(self):
         """The fitted model as a ``Falkon`` (alpha_, ny_points_, kernel, penalty): what predict_path, the heads and storage

@@ -1,5 +1,6 @@
 """Backend operations of the incremental FALKON model (odx/incremental.py), mixed into ``backend.HipBackend`` beside ``PathOps``
-and ``LeverageOps``: the M x M statistics of an f32 K_nM block (``knm_gram``: odx_knm_gram_f64) and the product of up to 8
+and ``LeverageOps``: the M x M statistics of an f32 K_nM block (``knm_gram``: odx_knm_gram_f64; with T right-hand
+sides from the same read, ``knm_gram_multi``: odx_knm_gram_rhsn_f64) and the product of up to 8
 vectors with them from one read (``symv``: odx_symvn_f64).  All HIP through libodx."""
 import torch
 
@@ -40,6 +41,40 @@ class IncrementalOps:
         hip.check(self.lib.odx_knm_gram_f64(_p(K.K), K.ld, n, M, _p(w), _p(y), float(beta), _p(G), G.stride(0) if M else 0, _p(b),
                                             self._stream()), "odx_knm_gram_f64")
         return G, b
+
+    def knm_gram_multi(self, K, w=None, Y=None, beta=1.0, G=None, B=None):
+        """knm_gram's G, bit for bit, and B[t] = beta B[t] + K' (w o Y[:, t]) for the T columns of Y from the SAME read of the
+        block (odx_knm_gram_rhsn_f64).  Y: (n, T) f64, a column per output, rows contiguous and 16-byte aligned with an even
+        row stride, 1 <= T <= 1024.  B: (T, >= M) f64, rows contiguous; None (with G None): a new (T, Mp) matrix, Mp = M rounded
+        up to even.  G, w, beta as knm_gram takes them.  Returns (G, B)."""
+        fmt = getattr(K, "fmt", "f32")
+        if fmt != "f32":
+            raise ValueError("knm_gram_multi: needs an f32-format K_nM block; this one is %r (statistics of compact blocks and "
+                             "streamed shards are not offered)" % (fmt,))
+        if getattr(K, "cmap", None) is not None:
+            raise ValueError("knm_gram_multi: not built for a block of distinct columns (a column map)")
+        n, M = K.n, K.M
+        if Y is None or Y.dtype != torch.float64 or Y.dim() != 2 or Y.shape[0] < n or not 1 <= Y.shape[1] <= 1024:
+            raise ValueError("knm_gram_multi: Y must be an f64 matrix of at least %d rows and 1 .. 1024 columns" % n)
+        T = Y.shape[1]
+        if Y.stride(1) != 1 or Y.stride(0) < T or Y.stride(0) % 2 or Y.data_ptr() % 16:
+            raise ValueError("knm_gram_multi: the rows of Y must be contiguous and 16-byte aligned (an even row stride)")
+        if G is None:
+            if B is not None:
+                raise ValueError("knm_gram_multi: G and B are given together or not at all")
+            G, beta = torch.empty((M, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device), 0.0
+            B = torch.empty((T, (M + 1) // 2 * 2), dtype=torch.float64, device=self.device)
+        elif G.dtype != torch.float64 or G.dim() != 2 or G.shape[0] < M or G.shape[1] < M or (M and G.stride(1) != 1):
+            raise ValueError("knm_gram_multi: G must be an f64 matrix of at least %d x %d, rows contiguous" % (M, M))
+        if B is None or B.dtype != torch.float64 or B.dim() != 2 or B.shape[0] != T or B.shape[1] < M or (M and B.stride(1) != 1) \
+                or (T > 1 and B.stride(0) < M):
+            raise ValueError("knm_gram_multi: B must be a (%d, >= %d) f64 matrix, rows contiguous" % (T, M))
+        if w is not None and (w.dtype != torch.float64 or w.numel() < n or not w.is_contiguous()):
+            raise ValueError("knm_gram_multi: w must be a contiguous f64 vector of at least %d" % n)
+        hip.check(self.lib.odx_knm_gram_rhsn_f64(_p(K.K), K.ld, n, M, _p(w), _p(Y), Y.stride(0), T, float(beta), _p(G),
+                                                 G.stride(0) if M else 0, _p(B), B.stride(0) if T > 1 else max(M, B.shape[1]),
+                                                 self._stream()), "odx_knm_gram_rhsn_f64")
+        return G, B
 
     def symv(self, G, X, alpha=1.0, out=None):
         """out[q, :M] = alpha * G X[q, :M] for the nv <= 8 rows of X (nv, Mp) from ONE read of the (M, ld) f64 matrix G

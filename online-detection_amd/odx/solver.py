@@ -123,6 +123,7 @@ class _Rows:
         self.AX = mat() if fold else None
         self.v = (mat(), mat() if fold else None)
         self.send, self.recv = send, recv
+        self.groups = None              # (set by a driver whose states share T but not A: see _cg_run)
 
 
 def _slots(TT, CC, M, L=1, l=0):
@@ -193,22 +194,28 @@ def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared=None, fold_rows
 
     shared: the _Rows whose matrices the vectors of ALL states are rows of, state l row l — the driver's statement that they
     share one P and lam and that the backend has trmvn: every triangular product of the L states is then one be.trmvn.
-    Without it _cg_run issues one be.trmv per state and product."""
+    Without it _cg_run issues one be.trmv per state and product.  A _Rows with `groups` ((P, lam, first row, end row) each:
+    the members of a lambda path over statistics, _fit_stats_members) states instead that the states of a group share P and
+    lam and that ALL states share T: the products with A's factors are then one be.trmvn per group, the one with T's inverse
+    one be.trmvn over all rows (the one with its transpose carries the group's lam: one per group)."""
     acc = any(c.scores is not None for c in cgs)
     sh = shared
     if sh is not None:
         P, lam, L = cgs[0].P, cgs[0].lam, len(cgs)
+        groups = sh.groups or [(P, lam, 0, L)]
 
     def Wn(*pairs, rows=False):
         """W for states that share P: every triangular product of the L states from ONE read of its factor."""
         k = len(pairs)
         for j, (s, _) in enumerate(pairs):
-            be.trmvn(P, "LAit", getattr(sh, s), out=sh.v[j])                                   # A^-1 s
+            for Pg, _, a, b in groups:
+                be.trmvn(Pg, "LAit", getattr(sh, s)[a:b], out=sh.v[j][a:b])                    # A^-1 s
             be.trmvn(P, "LTit", sh.v[j], out=sh.send[j * L:(j + 1) * L])                       # T^-1 A^-1 s
         exchange(k, rows)
         for j, (_, out) in enumerate(pairs):
-            be.trmvn(P, "LTi", sh.recv[j * L:(j + 1) * L], alpha=1.0 / n, beta=lam, Z=sh.v[j], out=sh.U)    # T^-T cc / n + lam v
-            be.trmvn(P, "LAi", sh.U, out=getattr(sh, out))                                     # A^-T u
+            for Pg, lg, a, b in groups:
+                be.trmvn(Pg, "LTi", sh.recv[j * L + a:j * L + b], alpha=1.0 / n, beta=lg, Z=sh.v[j][a:b], out=sh.U[a:b])    # T^-T cc / n + lam v
+                be.trmvn(Pg, "LAi", sh.U[a:b], out=getattr(sh, out)[a:b])                      # A^-T u
 
     def W1(*pairs, rows=False, srows=False):
         """c.<out> = W c.<s> for every (s, out) of pairs and every state c, W = A^-T [ T^-T K'K (T^-1 A^-1 .) / n + lam A^-1 . ],
@@ -262,15 +269,17 @@ def _cg_run(be, cgs, exchange, n, maxiter, opt, can_fold, shared=None, fold_rows
         for c in cgs:
             be.cg_finish(c.R, c.Pv, c.state, opt.cg_epsilon, tol)
     if sh is not None:
-        be.trmvn(P, "LTit", be.trmvn(P, "LAit", sh.X, out=sh.U), out=sh.alpha)    # T^-1 A^-1 beta
+        for Pg, _, a, b in groups:
+            be.trmvn(Pg, "LAit", sh.X[a:b], out=sh.U[a:b])
+        be.trmvn(P, "LTit", sh.U, out=sh.alpha)                                   # T^-1 A^-1 beta
         for l, c in enumerate(cgs):
             c.alpha = sh.alpha[l, :P.M]
     else:
         for c in cgs:
             c.alpha = be.trmv(c.P, "LTit", be.trmv(c.P, "LAit", c.X), out=c.alpha)    # T^-1 A^-1 beta
     if opt.check_pivots:
-        for c in (cgs[:1] if sh is not None else cgs):      # (one shared preconditioner: one status word)
-            _check_pivots(be, c.P)
+        for Pc in ([g[0] for g in groups] if sh is not None else [c.P for c in cgs]):      # (a shared preconditioner: one status word)
+            _check_pivots(be, Pc)
 
 
 def falkon_fit(be, F, y, Zf, sigma, lam, maxiter=20, opt=None, n_total=None, allreduce=None, knm_out=None,
@@ -422,6 +431,69 @@ def falkon_fit_stats(be, G, b, n, P, lam, maxiter=20, opt=None):
     cgs = [_cg_state(be, P, float(lam), b[:M] / n, M, _slots(TT, CC, M), True, alpha)]
     _cg_run(be, cgs, exchange, n, maxiter, opt, True)
     return alpha
+
+
+def _fit_stats_members(be, G, B, n, Ps, lams, maxiter, opt):
+    """The L x T conjugate-gradient states (penalty l of the preconditioners Ps, right-hand side row t of B) over ONE pair of
+    statistics in lock step: state l T + t.  falkon_fit_stats' exchange for all of them: one be.symv over the k L T rows in play
+    (ceil(k L T / 8) reads of G; k = 2 at a full-residual iteration, which always folds).  Returns the alphas (L, T, M)."""
+    n = float(n)
+    if not n > 0.0:
+        raise ValueError("the statistics must hold a positive total weight, got n = %r" % (n,))
+    L, T, M = len(Ps), B.shape[0], Ps[0].M
+    S, Mp = L * T, (M + 1) // 2 * 2                      # (rows 16-byte aligned for odd M too)
+    TT, CC = be.zeros(2 * S * Mp).view(2 * S, Mp), be.zeros(2 * S * Mp).view(2 * S, Mp)
+
+    def exchange(k, rows):
+        be.symv(G, TT[:k * S], out=CC[:k * S])
+
+    sh = _Rows(be, S, Mp, True, TT, CC)
+    B0 = be.zeros(T * Mp).view(T, Mp)                    # row t: K' W Y[:, t] / n
+    B0[:, :M] = B[:, :M] / n
+    shared = None
+    if S > 1 and hasattr(be, "trmvn"):
+        shared = sh
+        sh.groups = [(Ps[l], lams[l], l * T, (l + 1) * T) for l in range(L)]
+        U = be.trmvn(Ps[0], "LTi", B0, out=sh.U[:T])     # T^-T b0 is every member's; B = A_l^-T of it
+        for P, _, a, b in sh.groups:
+            be.trmvn(P, "LAi", U, out=sh.B[a:b])
+    else:
+        for l in range(L):
+            for t in range(T):
+                sh.B[l * T + t, :M].copy_(be.trmv(Ps[l], "LAi", be.trmv(Ps[l], "LTi", B0[t, :M])))
+    cgs = []
+    for s in range(S):
+        c = _CG(P=Ps[s // T], lam=lams[s // T], B=sh.B[s, :M], X=sh.X[s, :M], R=sh.R[s, :M], Pv=sh.Pv[s, :M], AP=sh.AP[s, :M],
+                AX=sh.AX[s, :M], state=be.zeros(4), v=(sh.v[0][s, :M], sh.v[1][s, :M]), io=_slots(TT, CC, M, S, s),
+                alpha=None if shared is not None else sh.alpha[s, :M])
+        be.cg_init(c.B, c.X, c.R, c.Pv, c.state)
+        cgs.append(c)
+    _cg_run(be, cgs, exchange, n, maxiter, opt, True, shared)
+    alphas = be.zeros(S * M).view(L, T, M)
+    for s, c in enumerate(cgs):
+        alphas[s // T, s % T].copy_(c.alpha)
+    return alphas
+
+
+def falkon_fit_stats_multi(be, G, B, n, P, lam, maxiter=20, opt=None):
+    """falkon_fit_stats for the T right-hand sides B ((T, >= M) f64, row t = K_nM' W Y[:, t]) of ONE G: T conjugate-gradient
+    states that share the preconditioner P, each following falkon_fit_stats' schedule with its own device-side stop flag.  Per
+    iteration ceil(k T / 8) reads of G (be.symv; k = 2 at a full-residual iteration, folded as in falkon_fit_stats, else 1) and
+    every triangular product of all T states from one read of its factor per 8 (be.trmvn).  No host synchronisation inside the
+    loop.  Returns the alphas (T, M) f64, row t for column t."""
+    return _fit_stats_members(be, G, B, n, [P], [float(lam)], maxiter, opt or SolverOptions())[0]
+
+
+def falkon_fit_stats_path(be, G, B, n, Ps, lams, maxiter=20, opt=None):
+    """falkon_fit_stats_multi at every penalty of `lams` from the same statistics: Ps is what be.precond_path returns for them
+    (the members share T's factors and own A's).  The L T states advance in lock step: per iteration ceil(k L T / 8) reads of G,
+    the products with T's inverse for all L T states at once, those with A_l's factors for the T states of member l.  No row is
+    touched, and the host does not synchronise inside the loop.  Returns the alphas (L, T, M) f64, in the order of `lams`."""
+    lams = [float(x) for x in lams]
+    if not lams or len(Ps) != len(lams) or any(not (math.isfinite(x) and x > 0.0) for x in lams):
+        raise ValueError("falkon_fit_stats_path: lams must be a non-empty sequence of finite positive penalties, one per member "
+                         "of Ps, got %r" % (lams,))
+    return _fit_stats_members(be, G, B, n, list(Ps), lams, maxiter, opt or SolverOptions())
 
 
 def falkon_fit_path(be, F, y, Zf, sigma, lams, maxiter=20, opt=None, n_total=None, allreduce=None, phase=None, knm_out=None,

@@ -9,7 +9,15 @@
   (c) partial_fit of a batch of new rows onto a model that has seen many, against InCoreFalkon.fit on all rows with the same
       centres, and the break-even batch size
 
-Usage: python tools/time_incremental.py [--part a|b|c] [--reps R]
+With --outputs T[,T...] (profiles/incremental_multi.md), instead of the parts above:
+
+  (d) odx_knm_gram_rhsn_f64 alone at nt = 1, 8, 32 and 64 against odx_knm_gram_f64 with one y on the same 1 GiB f32 chunk
+      (M = 2048 and M = 8192), alternating
+  (e) per T: partial_fit (solve=False) of one batch of 2e5 rows, D = 1024, M = 2048 into a model of T outputs against T
+      one-output models fed the same batch, and solve() likewise
+  (f) per T: solve_path with 8 penalties against 8 calls of solve(penalty)
+
+Usage: python tools/time_incremental.py [--part a|b|c|d|e|f] [--reps R] [--outputs T[,T...]]
 Prints one JSON line per measurement: median, min and max of the repetitions in ms."""
 import argparse
 import json
@@ -215,12 +223,114 @@ def part_c(be, reps):
            breakeven_batch_rows=breakeven)
 
 
+def part_d(be, reps):
+    from odx.backend import Knm
+    for M in (2048, 8192):
+        K = Knm()
+        K.M, K.ld = M, M
+        K.n = n = (1 << 30) // (4 * M)                           # a 1 GiB f32 chunk
+        K.K = torch.rand((n, M), dtype=torch.float32, device="cuda")
+        w = torch.randn(n, dtype=torch.float64, device="cuda")
+        Y = torch.randn((n, 64), dtype=torch.float64, device="cuda")
+        y = Y[:, 0].contiguous()
+        G = torch.zeros((M, M), dtype=torch.float64, device="cuda")
+        b = torch.zeros(M, dtype=torch.float64, device="cuda")
+        B = torch.zeros((64, M), dtype=torch.float64, device="cuda")
+        nts = (1, 8, 32, 64)
+
+        def one():
+            be.knm_gram(K, w=w, y=y, beta=1.0, G=G, b=b)
+
+        def multi(nt):
+            return lambda: be.knm_gram_multi(K, w=w, Y=Y[:, :nt], beta=1.0, G=G, B=B[:nt])
+
+        ts = alternate([one] + [multi(nt) for nt in nts], reps)
+        tiles_m = (M + 127) // 128
+        base = float(np.median(ts[0]))
+        report("gram_rhsn", n=n, M=M, knm_gram_one_y=ts[0], expected_extra_percent=round(100.0 * tiles_m / (tiles_m * (tiles_m + 1)), 2),
+               **{"rhsn_nt%d" % nt: t for nt, t in zip(nts, ts[1:])},
+               **{"extra_percent_nt%d" % nt: round(100.0 * (float(np.median(t)) / base - 1.0), 2) for nt, t in zip(nts, ts[1:])})
+        del K, G, B, Y, w
+
+
+def _batch_problem(T, n=200000, D=1024, M=2048):
+    g = torch.Generator(device="cuda")
+    g.manual_seed(5)
+    X = torch.randn((n, D), dtype=torch.float32, device="cuda", generator=g)
+    Y = torch.where(torch.randn((n, T), dtype=torch.float64, device="cuda", generator=g) > 0, 1.0, -1.0)
+    return X, Y, X[:M].contiguous()
+
+
+def part_e(be, reps, T):
+    sigma, lam = 30.0, 1e-5
+    X, Y, Z = _batch_problem(T)
+    multi = odx.IncrementalFalkon(odx.GaussianKernel(sigma), lam, centres=Z, outputs=T)
+    ones = [odx.IncrementalFalkon(odx.GaussianKernel(sigma), lam, centres=Z) for _ in range(T)]
+
+    def add_multi():
+        multi.partial_fit(X, Y, decay=0.0, solve=False)
+        torch.cuda.synchronize()
+
+    def add_ones():
+        for t, m in enumerate(ones):
+            m.partial_fit(X, Y[:, t:t + 1], decay=0.0, solve=False)
+        torch.cuda.synchronize()
+
+    def solve_multi():
+        multi.solve()
+        torch.cuda.synchronize()
+
+    def solve_ones():
+        for m in ones:
+            m.solve()
+        torch.cuda.synchronize()
+
+    ta, tb = alternate([add_multi, add_ones], reps)
+    tc, td = alternate([solve_multi, solve_ones], reps)
+    diff = max(float((multi.alpha_[:, t] - ones[t].alpha_[:, 0]).norm() / ones[t].alpha_.norm()) for t in range(T))
+    report("partial_fit_outputs", T=T, rows=X.shape[0], D=X.shape[1], M=Z.shape[0], add_outputs_T=ta, add_T_one_output_models=tb,
+           solve_outputs_T=tc, solve_T_one_output_models=td, add_speedup=round(float(np.median(tb) / np.median(ta)), 2),
+           solve_speedup=round(float(np.median(td) / np.median(tc)), 2), max_alpha_rel_diff=diff)
+
+
+def part_f(be, reps, T):
+    sigma = 30.0
+    pens = [10.0 ** -k for k in (2.0, 2.5, 3.0, 3.5, 4.0, 4.5, 5.0, 5.5)]
+    X, Y, Z = _batch_problem(T, n=50000)
+    est = odx.IncrementalFalkon(odx.GaussianKernel(sigma), pens[0], centres=Z, outputs=T).partial_fit(X, Y, solve=False)
+
+    def path():
+        est.solve_path(pens)
+        torch.cuda.synchronize()
+
+    def loop():
+        for p in pens:
+            est.solve(penalty=p)
+        torch.cuda.synchronize()
+
+    tp, tl = alternate([path, loop], reps)
+    report("solve_path", T=T, M=Z.shape[0], penalties=len(pens), solve_path=tp, solve_per_penalty=tl,
+           speedup=round(float(np.median(tl) / np.median(tp)), 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="abc")
+    ap.add_argument("--part", default=None)
     ap.add_argument("--reps", type=int, default=21)
+    ap.add_argument("--outputs", default=None, help="T[,T...]: time the multi-output route (parts d, e, f) at these widths")
     a = ap.parse_args()
     be = odx.get_backend()
+    if a.outputs is not None:
+        part = a.part or "def"
+        if "d" in part:
+            part_d(be, a.reps)
+        for T in [int(t) for t in a.outputs.split(",")]:
+            if "e" in part:
+                part_e(be, max(5, a.reps // 4), T)
+            if "f" in part:
+                part_f(be, max(5, a.reps // 4), T)
+        return
+    a.part = a.part or "abc"
     if "a" in a.part:
         part_a(be, a.reps)
     if "b" in a.part:
